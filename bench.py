@@ -19,6 +19,11 @@ slowest rank's time).  Weak scaling: per-GPU work is fixed as N grows.
 The reference publishes no numbers, so vs_baseline is null; the reference's
 operating point (60 encoded FPS per session, one session per GPU) is reported as
 `vs_operating_point` = value / (60 * N).
+
+A plain run sets up, warms up, times `--steps` steps and prints the result line.  `--full` adds the
+untimed probes after the timed steps (per-region quality, paced session density, IDR storm, the
+serving configuration's density in a child process); their fields are null in a plain run.
+`--dump-outputs DIR` writes what the last timed step produced as DIR/<name>.npy (dump_outputs).
 """
 from __future__ import annotations
 
@@ -274,6 +279,7 @@ class CpuSession:
         cfg.enc.width, cfg.enc.height, cfg.enc.fps = cfg.width, cfg.height, cfg.fps
         self.enc = N.CpuH264Encoder(cfg.enc)
         self.fps = cfg.fps
+        self.fake_clock = bool(cfg.fake_clock)  # as Session: the barcode's timestamp from the frame number
         self.n = 0
 
     def step(self, force_idr: bool = False, quality: bool = True):
@@ -282,7 +288,8 @@ class CpuSession:
         import numpy as np
 
         t0 = time.monotonic()
-        img = self.desk.render(self.n, self.n / self.fps, int(t0 * 1e6))
+        stamp = self.n * 1000000 // max(1, self.fps) if self.fake_clock else int(t0 * 1e6)
+        img = self.desk.render(self.n, self.n / self.fps, stamp)
         y, uv = self._conv(img)
         au = self.enc.encode(y, uv, force_idr)
         t1 = time.monotonic()
@@ -306,6 +313,45 @@ class CpuSession:
         return types.SimpleNamespace(au=au, qp=st.qp, psnr_y=py_, psnr_y_masked=py_, psnr_u=psnr(su, w * h / 4),
                                      psnr_v=psnr(sv, w * h / 4), gpu_ms=0.0, t_capture_us=t0 * 1e6,
                                      t_encoded_us=t1 * 1e6)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname: str, results: list, sessions: list, K: int) -> None:
+    """--dump-outputs: what the timed path handed its caller, as DIR/<name>.npy (float32 / float64).
+
+    Per session (names carry `_s<k>` when there is more than one): `au`, the bytes of the last timed
+    step's access unit; `au_bytes`, `qp`, `frame_id` and `psnr` (columns Y, U, V), one row per timed
+    step; and, for session 0, `recon_y` / `recon_uv`, the encoder's reconstruction of the last
+    step's picture (the frame the decoder shows).  With the barcode's clock tied to the frame
+    number (main() sets SessionConfig.fake_clock for a dumping run) the same arguments give the
+    same source frames, so two builds can be compared array for array."""
+    import numpy as np
+
+    out = {}
+    for k in range(K):
+        sfx = f"_s{k}" if K > 1 else ""
+        rs = results[k::K]  # results are frame-major: session k's frames
+        out["au" + sfx] = np.frombuffer(bytes(rs[-1].au), np.uint8).astype(np.float32)
+        out["au_bytes" + sfx] = np.array([len(r.au) for r in rs], np.float64)
+        out["qp" + sfx] = np.array([r.qp for r in rs], np.float64)
+        out["frame_id" + sfx] = np.array([getattr(r, "frame_id", i) for i, r in enumerate(rs)], np.float64)
+        out["psnr" + sfx] = np.array([[r.psnr_y, r.psnr_u, r.psnr_v] for r in rs], np.float64)
+    s0 = sessions[0]
+    ry, ruv = s0.recon() if hasattr(s0, "recon") else s0.enc.recon()
+    out["recon_y"], out["recon_uv"] = ry.astype(np.float32), ruv.astype(np.float32)
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_LIMIT_BYTES:  # a very large picture: a fixed, seeded sample of the reconstruction
+        rng = np.random.default_rng(0)
+        for name in ("recon_y", "recon_uv"):
+            a = out[name].ravel()
+            keep = max(1, int(a.size * (DUMP_LIMIT_BYTES / 2) / total))
+            out[name] = a[np.sort(rng.choice(a.size, keep, replace=False))]
+    d = Path(dirname)
+    d.mkdir(parents=True, exist_ok=True)
+    for name, a in out.items():
+        np.save(d / (name + ".npy"), a)
 
 
 def serving_probe(args, dev_index: int) -> dict | None:
@@ -368,8 +414,16 @@ def main() -> None:
                          "under a screen-fixed video-like panel; no noise panel), or subpel (a fractional pan of "
                          "2.5 px right / 0.75 px down per frame, bilinearly resampled, under a zooming video panel: "
                          "quarter-sample motion, the interpolation filters and the deblocking decision exercised)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the untimed probes (--quality-probe, --density-probe, "
+                         "--serving-probe); a plain run only sets up, warms up, times --steps and prints its line, "
+                         "with those probes' fields null")
+    ap.add_argument("--dump-outputs", type=str, default="", metavar="DIR",
+                    help="after the timed steps write what the last one produced (access unit, per-step sizes / QP / "
+                         "PSNR, the reconstructed picture) as DIR/<name>.npy; the barcode's clock then follows the "
+                         "frame number, so the same arguments give the same frames in every run")
     ap.add_argument("--quality-probe", type=int, default=30,
-                    help="untimed frames after the run with per-region / chroma PSNR read back (0: off)")
+                    help="--full: untimed frames after the run with per-region / chroma PSNR read back (0: off)")
     ap.add_argument("--aq", type=int, default=None,
                     help="adaptive quantisation: 0 off, 1 coarser QP for noise-like MBs, 2 + rate-distortion "
                          "residual drop for them (default: the encoder's)")
@@ -402,11 +456,11 @@ def main() -> None:
     ap.add_argument("--sessions-per-gpu", type=int, default=1,
                     help="concurrent sessions per GPU (density): each has its own HIP stream and one frame in flight")
     ap.add_argument("--density-probe", type=int, default=1,
-                    help="after the timed run, measure how many paced 1080p60 sessions this GPU sustains in this "
+                    help="--full: after the timed run, measure how many paced 1080p60 sessions this GPU sustains in this "
                          "process (doubling K until a 60 fps slot is missed, then bisecting); reported, never part "
                          "of `value`")
     ap.add_argument("--serving-probe", type=int, default=1,
-                    help="GPU: also run the paced and IDR-storm density probes in the serving path's configuration "
+                    help="--full, GPU: also run the paced and IDR-storm density probes in the serving path's configuration "
                          "(a child process with the 16 hardware queues `mxdesk serve --sessions K` sets, "
                          "mxdesk/cli.py); reported beside the in-process probes, never part of `value`")
     ap.add_argument("--density-only", type=int, default=0, help=argparse.SUPPRESS)  # the serving-probe child
@@ -440,6 +494,8 @@ def main() -> None:
         args.depth = min(args.depth or 4, 4)  # the VP8 encoder keeps at most four frames in flight
     if args.depth is None:
         args.depth = 3
+    if not args.full:  # a plain run: the timed steps only
+        args.quality_probe = args.density_probe = args.serving_probe = 0
     content = {"desktop": 0, "motion": 1, "subpel": 2}[args.content]
     if content:
         args.noise = 0  # the motion content has a video panel instead of the noise panel
@@ -513,6 +569,8 @@ def main() -> None:
         cfg.enc.intra4x4 = args.intra4x4
     cfg.noise = args.noise
     cfg.content = content
+    if args.dump_outputs:
+        cfg.fake_clock = 1  # the barcode's timestamp from the frame number: identical frames run to run
     cfg.use_graph = args.graph
     cfg.capture_stream = args.capture_stream
     cfg.enc.pipeline_depth = args.depth
@@ -591,6 +649,9 @@ def main() -> None:
         dbk.append(getattr(r, "deblocked", 0))
         dbc.append((getattr(r, "db_coherent", 0), getattr(r, "db_moving", 0)))
 
+    if args.dump_outputs and rank == 0:  # before any probe steps the sessions further
+        dump_outputs(args.dump_outputs, results, sessions, K)
+
     quality = None
     if args.quality_probe > 0 and rank == 0 and not args.out_width:
         quality = quality_probe(sessions[0], args.width, args.height, content, args.noise, args.quality_probe)
@@ -651,6 +712,7 @@ def main() -> None:
             "warmup": args.warmup,
             "ms_per_step": round(elapsed_max / args.steps * 1000.0, 4),
             "higher_is_better": True,
+            "full": bool(args.full),
             "scaling": "weak",
             "vs_baseline": None,
             "vs_operating_point": round(fps_total / (60.0 * world), 3),

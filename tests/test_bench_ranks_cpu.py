@@ -45,9 +45,10 @@ def _check(r, n):
 
 
 def test_bench_self_launches_ranks_without_world_size():
-    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2"] + ARGS, cwd=ROOT, env=_env(),
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--full"] + ARGS, cwd=ROOT, env=_env(),
                        capture_output=True, text=True, timeout=300)
     out = _check(r, 2)
+    # (the density probe runs with --full)
     # the node metric is every rank's own measured density, summed (VERDICT r5 weak #3b)
     by_rank = out["sessions_per_gpu_measured_by_rank"]
     assert len(by_rank) == 2 and all(isinstance(k, int) for k in by_rank)
@@ -88,3 +89,27 @@ def test_bench_single_gpu_default():
                        capture_output=True, text=True, timeout=300)
     out = _check(r, 1)
     assert out["mean_psnr_y_db"] > 30
+    # a plain run times its steps only: no probe ran
+    assert out["full"] is False and out["density_probe"] is None and out["sessions_per_node_measured"] is None
+
+
+def test_bench_dump_outputs_is_reproducible(tmp_path):
+    """--dump-outputs: float .npy files of what the last timed step produced, the same from run to
+    run (the barcode's clock follows the frame number), and --steps sets the timed steps."""
+    import numpy as np
+
+    dumps = []
+    for d in (tmp_path / "a", tmp_path / "b"):
+        r = subprocess.run([sys.executable, str(ROOT / "bench.py")] + ARGS + ["--dump-outputs", str(d)], cwd=ROOT,
+                           env=_env(), capture_output=True, text=True, timeout=300)
+        out = _check(r, 1)
+        dumps.append({p.stem: np.load(p) for p in sorted(d.glob("*.npy"))})
+    a, b = dumps
+    assert set(a) == set(b) == {"au", "au_bytes", "qp", "frame_id", "psnr", "recon_y", "recon_uv"}
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    steps = out["steps"]
+    assert steps == 6 and a["au_bytes"].shape == (steps,) and a["psnr"].shape == (steps, 3)
+    assert a["au"].size == a["au_bytes"][-1] and a["recon_y"].shape[0] >= 144 and a["recon_y"].shape[1] >= 256
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k

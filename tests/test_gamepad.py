@@ -4,6 +4,7 @@ import asyncio
 import os
 import shutil
 import subprocess
+import tempfile
 from pathlib import Path
 
 import pytest
@@ -22,8 +23,18 @@ def test_parse_gamepad_messages():
     assert parse_message("js,d,2").extra == {"op": "d", "idx": 2}
 
 
+@pytest.fixture
+def sock_dir():
+    """A short directory for the pads' unix sockets: sockaddr_un.sun_path holds 108 bytes, and
+    pytest's tmp_path under a deep TMPDIR is longer than that."""
+    base = "/tmp" if os.access("/tmp", os.W_OK | os.X_OK) else None
+    with tempfile.TemporaryDirectory(prefix="mxjs", dir=base) as d:
+        assert len(os.path.join(d, "mxdesk_js0.sock")) < 100, d
+        yield Path(d)
+
+
 @pytest.mark.skipif(shutil.which("gcc") is None, reason="no C compiler")
-def test_interposer_end_to_end(tmp_path):
+def test_interposer_end_to_end(tmp_path, sock_dir):
     from mxdesk import _build
 
     lib = _build.build_interposer()
@@ -32,11 +43,11 @@ def test_interposer_end_to_end(tmp_path):
     subprocess.run(["gcc", "-O1", "-o", str(exe), str(HERE / "native/js_reader.c")], check=True)
 
     async def go():
-        srv = GamepadServer(tmp_path)
+        srv = GamepadServer(sock_dir)
         await srv.start()
         srv.apply(parse_message("js,c,0,bXhkZXNrIHBhZA==,6,17"))
         env = dict(os.environ)
-        env["MXDESK_JS_DIR"] = str(tmp_path)
+        env["MXDESK_JS_DIR"] = str(sock_dir)
         env["LD_PRELOAD"] = str(lib) + (":" + env["LD_PRELOAD"] if env.get("LD_PRELOAD") else "")
         proc = await asyncio.create_subprocess_exec(str(exe), "3", env=env, stdout=asyncio.subprocess.PIPE,
                                                     stderr=asyncio.subprocess.PIPE)

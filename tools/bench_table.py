@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Summarise bench.py JSON files: one row per file (fps, p50, kbps, QP, masked PSNR, density)."""
+"""Summarise bench.py JSON files: one row per file (fps, p50, kbps, QP, masked PSNR, density).
+The density and quality-probe columns need a `bench.py --full` run; a plain run shows None there."""
 import json
 import sys
 

@@ -8,7 +8,8 @@
 #   tests               pytest -m gpu (one process)
 #   pytest:NAME:ARGS    pytest -m gpu ARGS (test files / -k filters) -> OUT/pytest_NAME.log
 #   smoke               __graft_entry__.smoke()
-#   bench:NAME[:ARGS]   python bench.py ARGS  -> OUT/NAME.json  (ARGS: comma-separated flags)
+#   bench:NAME[:ARGS]   python bench.py ARGS  -> OUT/NAME.json  (ARGS: comma-separated flags; --full adds
+#                       the density / IDR-storm / serving / quality probes to the timed steps)
 #   prof:NAME[:ARGS]    rocprofv3 --kernel-trace --stats around bench.py ARGS -> OUT/prof_NAME/
 #   pmc:NAME:CTRS[:ARGS] rocprofv3 --pmc CTRS (comma list) around bench.py ARGS -> OUT/pmc_NAME/
 #   py:NAME:SCRIPT[:ARGS] python SCRIPT ARGS -> OUT/NAME.log
