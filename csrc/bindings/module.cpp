@@ -118,6 +118,14 @@ PYBIND11_MODULE(_native, m) {
         }
         return out;
     });
+    h.def("mc_luma_gpu", [](py::array_t<uint8_t, py::array::c_style> ref, int coded_w, int x4, int y4) {
+        if (ref.ndim() != 2 || coded_w % 16 || ref.shape(0) % 16 || ref.shape(1) < coded_w)
+            throw std::invalid_argument("ref must be (coded_h, pitch) with 16-aligned coded size");
+        py::array_t<uint8_t> out({16, 16});
+        h264::mc_luma_for_test(ref.data(), coded_w, (int)ref.shape(0), (int)ref.shape(1), x4, y4, out.mutable_data());
+        return out;
+    }, py::arg("ref"), py::arg("coded_w"), py::arg("x4"), py::arg("y4"),
+          "16x16 luma prediction at quarter-sample position (x4, y4) by k_inter_encode's interpolation");
     h.def("cavlc_block", &cavlc_block_py, py::arg("coef"), py::arg("nc"));
     h.def("fdct4x4", &fdct_py);
     h.def("idct4x4", &idct_py);

@@ -238,6 +238,25 @@ std::vector<std::vector<uint8_t>> hpel_planes_for_test(const uint8_t* ref, int c
     return out;
 }
 
+void mc_luma_for_test(const uint8_t* ref, int coded_w, int coded_h, int pitch, int x4, int y4, uint8_t* out) {
+    Geometry g{};
+    g.width = g.coded_w = coded_w;
+    g.height = g.coded_h = coded_h;
+    g.mb_w = coded_w / 16;
+    g.mb_h = coded_h / 16;
+    g.pitch = pitch;
+    uint8_t *dref = nullptr, *dout = nullptr;
+    HIP_CHECK(hipMalloc(&dref, (size_t)pitch * coded_h));
+    HIP_CHECK(hipMalloc(&dout, 256));
+    HIP_CHECK(hipMemcpy(dref, ref, (size_t)pitch * coded_h, hipMemcpyHostToDevice));
+    launch_mc_luma_test(g, dref, x4, y4, dout, nullptr);
+    const hipError_t e = hipGetLastError();
+    if (e == hipSuccess) (void)hipMemcpy(out, dout, 256, hipMemcpyDeviceToHost);
+    (void)hipFree(dref);
+    (void)hipFree(dout);
+    HIP_CHECK(e);
+}
+
 // ------------------------------------------------------------------ GpuH264Encoder
 // Events that only order GPU work between this device's queues: a device-scope release when
 // recorded (the default system-scope release writes the caches back for the host each time).
@@ -282,7 +301,6 @@ void GpuH264Encoder::alloc_slot(FrameSlot& sl) {
     HIP_CHECK(hipEventCreateWithFlags(&sl.start, hipEventDisableTiming));
     HIP_CHECK(hipEventCreateWithFlags(&sl.analysis_done, kDeviceEvent));
     HIP_CHECK(hipEventCreateWithFlags(&sl.deblock_done, kDeviceEvent));
-    HIP_CHECK(hipEventCreateWithFlags(&sl.hpel_done, kDeviceEvent));
     HIP_CHECK(hipEventCreateWithFlags(&sl.me_done, kDeviceEvent));
     HIP_CHECK(hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
 }
@@ -297,7 +315,7 @@ void GpuH264Encoder::free_slot(FrameSlot& sl) {
     if (b.db_err) (void)hipHostFree(b.db_err);
     if (sl.fs_host) (void)hipHostFree(sl.fs_host);
     if (sl.host_out) (void)hipHostFree(sl.host_out);
-    for (hipEvent_t e : {sl.start, sl.analysis_done, sl.deblock_done, sl.done, sl.hpel_done, sl.me_done})
+    for (hipEvent_t e : {sl.start, sl.analysis_done, sl.deblock_done, sl.done, sl.me_done})
         if (e) (void)hipEventDestroy(e);
 }
 
@@ -339,33 +357,12 @@ GpuH264Encoder::GpuH264Encoder(const EncoderConfig& cfg, hipStream_t stream)
         for (int mx = mask_mb_[0]; mx < mask_mb_[2]; ++mx)
             masked_pixels_ -= (int64_t)std::max(0, std::min(16, cfg.width - 16 * mx)) *
                               std::max(0, std::min(16, cfg.height - 16 * my));
-    hp_pitch_ = (geom_.coded_w + 2 * kHpelPad + 255) & ~255;
-    const size_t hp_bytes = (size_t)hp_pitch_ * (geom_.coded_h + 2 * kHpelPad);
-    for (int i = 0; i < 4; ++i) HIP_CHECK(hipMalloc(&hp_[i], hp_bytes));
-    if (cfg_.h264_deblock())
-        for (int i = 0; i < 4; ++i) HIP_CHECK(hipMalloc(&hpu_[i], hp_bytes));
+    if (cfg_.h264_deblock()) HIP_CHECK(hipMalloc(&rec_unf_, ysz));
     for (int i = 0; i < depth_; ++i) alloc_slot(slots_[i]);
     clock_khz_ = device_clock_khz();
     if (depth_ > 1) {
         HIP_CHECK(hipStreamCreateWithFlags(&stream_e_, hipStreamNonBlocking));
-        HIP_CHECK(hipStreamCreateWithFlags(&stream_a_, hipStreamNonBlocking));
-        HIP_CHECK(hipEventCreateWithFlags(&ref_ready_, kDeviceEvent));
-        HIP_CHECK(hipEventRecord(ref_ready_, stream_));
         if (cfg_.h264_deblock()) {
-            // The side-stream search may keep every CU busy just as the previous picture's
-            // k_deblock starts: MXDESK_ME_CU_RESERVE=n (default 0) keeps the search off n compute
-            // units (a CU mask on its stream), so the filter's row waves find CUs of their own
-            const char* rv = std::getenv("MXDESK_ME_CU_RESERVE");
-            const int reserve = rv ? std::atoi(rv) : 0;
-            int ncu = 0;
-            HIP_CHECK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, 0));
-            if (reserve > 0 && reserve < ncu) {
-                std::vector<uint32_t> mask((size_t)(ncu + 31) / 32, 0u);
-                for (int c = 0; c < ncu - reserve; ++c) mask[(size_t)c / 32] |= 1u << (c % 32);
-                HIP_CHECK(hipExtStreamCreateWithCUMask(&stream_m_, (uint32_t)mask.size(), mask.data()));
-            } else {
-                HIP_CHECK(hipStreamCreateWithFlags(&stream_m_, hipStreamNonBlocking));
-            }
             HIP_CHECK(hipEventCreateWithFlags(&ev_hpu_, kDeviceEvent));
             HIP_CHECK(hipEventRecord(ev_hpu_, stream_));
         }
@@ -378,12 +375,28 @@ GpuH264Encoder::GpuH264Encoder(const EncoderConfig& cfg, hipStream_t stream)
     }
 }
 
-void GpuH264Encoder::set_hpel_side_stream(bool on) {
-    hpel_side_ = on;
-    if (!on && stream_a_) {  // its hardware queue is better left to the session's other streams
-        HIP_CHECK(hipStreamSynchronize(stream_a_));
-        HIP_CHECK(hipStreamDestroy(stream_a_));
-        stream_a_ = nullptr;
+void GpuH264Encoder::ensure_me_stream() {
+    if (stream_m_) return;
+    e2_retired_ = true;
+    if (stream_e2_) {  // its hardware queue goes to the side search: the chains already queued finish first
+        drain_launcher();
+        HIP_CHECK(hipStreamSynchronize(stream_e2_));
+        HIP_CHECK(hipStreamDestroy(stream_e2_));
+        stream_e2_ = nullptr;
+    }
+    // The side-stream search may keep every CU busy just as the previous picture's
+    // k_deblock starts: MXDESK_ME_CU_RESERVE=n (default 0) keeps the search off n compute
+    // units (a CU mask on its stream), so the filter's row waves find CUs of their own
+    const char* rv = std::getenv("MXDESK_ME_CU_RESERVE");
+    const int reserve = rv ? std::atoi(rv) : 0;
+    int ncu = 0;
+    HIP_CHECK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, 0));
+    if (reserve > 0 && reserve < ncu) {
+        std::vector<uint32_t> mask((size_t)(ncu + 31) / 32, 0u);
+        for (int c = 0; c < ncu - reserve; ++c) mask[(size_t)c / 32] |= 1u << (c % 32);
+        HIP_CHECK(hipExtStreamCreateWithCUMask(&stream_m_, (uint32_t)mask.size(), mask.data()));
+    } else {
+        HIP_CHECK(hipStreamCreateWithFlags(&stream_m_, hipStreamNonBlocking));
     }
 }
 
@@ -400,10 +413,10 @@ void GpuH264Encoder::launcher_loop() {
         }
         try {
             FrameSlot& sl = slots_[j.slot];
-            HIP_CHECK(hipStreamWaitEvent(stream_e_, sl.analysis_done, 0));
-            launch_entropy(geom_, sl.buf, sl.host_out, stream_e_, j.sse_ready);
+            HIP_CHECK(hipStreamWaitEvent(j.stream, sl.analysis_done, 0));
+            launch_entropy(geom_, sl.buf, sl.host_out, j.stream, j.sse_ready);
             HIP_CHECK(hipGetLastError());
-            HIP_CHECK(hipEventRecord(sl.done, stream_e_));
+            HIP_CHECK(hipEventRecord(sl.done, j.stream));
         } catch (...) {
             std::lock_guard<std::mutex> lk(lmu_);
             lerr_ = std::current_exception();
@@ -445,24 +458,21 @@ GpuH264Encoder::~GpuH264Encoder() {
         (void)hipStreamSynchronize(stream_e_);
         (void)hipStreamDestroy(stream_e_);
     }
-    if (stream_a_) {
-        (void)hipStreamSynchronize(stream_a_);
-        (void)hipStreamDestroy(stream_a_);
+    if (stream_e2_) {
+        (void)hipStreamSynchronize(stream_e2_);
+        (void)hipStreamDestroy(stream_e2_);
     }
-    if (ref_ready_) (void)hipEventDestroy(ref_ready_);
     if (stream_m_) {
         (void)hipStreamSynchronize(stream_m_);
         (void)hipStreamDestroy(stream_m_);
     }
     if (ev_hpu_) (void)hipEventDestroy(ev_hpu_);
-    for (int i = 0; i < 4; ++i)
-        if (hpu_[i]) (void)hipFree(hpu_[i]);
+    if (rec_unf_) (void)hipFree(rec_unf_);
     for (int i = 0; i < 2; ++i) {
         (void)hipFree(rec_y_[i]);
         (void)hipFree(rec_uv_[i]);
         (void)hipFree(src_keep_[i]);
     }
-    for (int i = 0; i < 4; ++i) (void)hipFree(hp_[i]);
     for (int i = 0; i < depth_; ++i) free_slot(slots_[i]);
 }
 
@@ -480,15 +490,10 @@ void GpuH264Encoder::enqueue_analysis_kernels(bool idr, const uint8_t* src_y, co
         if (cfg_.aq >= 3)  // the next P picture's previous source (P pictures: k_inter_encode stores it)
             launch_save_src(geom_, sl.buf, src_y, stream_);
     } else {
-        // MXDESK_INPUT_WAIT=early: the capture hand-off waited before k_hpel (next to the previous
-        // frame's analysis_done record) instead of after it -- experiment on queue barrier costs
-        static const bool early = [] {
-            const char* e = std::getenv("MXDESK_INPUT_WAIT");
-            return e && std::string(e) == "early";
-        }();
-        if (early) wait_input();
         // the search of a picture whose reference was deblocked reads that reference's unfiltered
-        // planes (hpu_): on the side stream, it overlaps the reference's k_deblock
+        // luma (rec_unf_): on the side stream, it overlaps the reference's k_deblock.  The search is
+        // the picture's first kernel: it publishes the frame state on whichever stream it runs
+        if (depth_ > 1 && pub && sl.me_unf) ensure_me_stream();
         const bool side_me = stream_m_ && pub && sl.me_unf;
         if (side_me) {
             HIP_CHECK(hipStreamWaitEvent(stream_m_, ev_hpu_, 0));
@@ -496,22 +501,13 @@ void GpuH264Encoder::enqueue_analysis_kernels(bool idr, const uint8_t* src_y, co
                 HIP_CHECK(hipStreamWaitEvent(stream_m_, in_ev_, 0));
                 in_ev_ = nullptr;  // the analysis stream waits for the search, so for the input too
             }
-            launch_me(geom_, sl.buf, src_y, stream_m_, pub);
+            launch_me(geom_, sl.buf, src_y, stream_m_, pub, true);
             HIP_CHECK(hipEventRecord(sl.me_done, stream_m_));
-        }
-        if (stream_a_ && hpel_side_ && pub && ref_seq_ + 1 == seq_) {  // the previous picture recorded ref_ready_
-            HIP_CHECK(hipStreamWaitEvent(stream_a_, ref_ready_, 0));
-            launch_hpel(geom_, sl.buf, hp_, hp_pitch_, stream_a_, pub);
-            HIP_CHECK(hipEventRecord(sl.hpel_done, stream_a_));
-            HIP_CHECK(hipStreamWaitEvent(stream_, sl.hpel_done, 0));
-        } else {
-            launch_hpel(geom_, sl.buf, hp_, hp_pitch_, stream_, pub);
-        }
-        wait_input();
-        if (side_me)
             HIP_CHECK(hipStreamWaitEvent(stream_, sl.me_done, 0));
-        else
-            launch_me(geom_, sl.buf, src_y, stream_);
+        } else {
+            wait_input();
+            launch_me(geom_, sl.buf, src_y, stream_, pub);
+        }
         launch_inter(geom_, sl.buf, src_y, src_uv, stream_);
         if (cfg_.intra_in_p) launch_intra_in_p(geom_, sl.buf, src_y, src_uv, stream_);
     }
@@ -531,11 +527,11 @@ void GpuH264Encoder::enqueue_entropy() {
     launch_entropy(geom_, sl.buf, sl.host_out, stream_e_ ? stream_e_ : stream_, nullptr);
 }
 
-void GpuH264Encoder::unfiltered_planes(FrameSlot& sl) {
-    // F/H/V/J planes of this picture's reconstruction before k_deblock filters it in place: the
-    // next picture's motion search (FrameState::me_*) reads them on the side stream
-    launch_hpel_of(geom_, sl.fs_host->rec_y, hpu_, hp_pitch_, stream_);
-    if (stream_m_) HIP_CHECK(hipEventRecord(ev_hpu_, stream_));
+void GpuH264Encoder::unfiltered_copy(FrameSlot& sl) {
+    // this picture's luma reconstruction before k_deblock filters it in place: the next picture's
+    // motion search (FrameState::me_ref) reads the copy, on the side stream with depth > 1
+    launch_copy_luma(geom_, sl.fs_host->rec_y, rec_unf_, stream_);
+    if (ev_hpu_) HIP_CHECK(hipEventRecord(ev_hpu_, stream_));
 }
 
 void GpuH264Encoder::enqueue_kernels(bool idr, const uint8_t* src_y, const uint8_t* src_uv, bool publish) {
@@ -546,20 +542,20 @@ void GpuH264Encoder::enqueue_kernels(bool idr, const uint8_t* src_y, const uint8
         HIP_CHECK(hipEventRecord(sl.analysis_done, stream_));
         hipEvent_t sse_ready = nullptr;
         if (sl.deblock) {
-            unfiltered_planes(sl);
+            unfiltered_copy(sl);
             launch_deblock(geom_, sl.buf, src_y, src_uv, stream_);
             HIP_CHECK(hipEventRecord(sl.deblock_done, stream_));
             sse_ready = sl.deblock_done;
         }
-        if (stream_a_ && hpel_side_ && publish) {
-            HIP_CHECK(hipEventRecord(ref_ready_, stream_));
-            ref_seq_ = seq_;
-        }
+        // depth >= 3: the chains of consecutive pictures alternate between two entropy streams
+        if (depth_ >= 3 && !stream_e2_ && !e2_retired_ && !stream_m_)
+            HIP_CHECK(hipStreamCreateWithFlags(&stream_e2_, hipStreamNonBlocking));
+        hipStream_t es = (stream_e2_ && (seq_ & 1)) ? stream_e2_ : stream_e_;
         HIP_CHECK(hipGetLastError());
         {
             std::lock_guard<std::mutex> lk(lmu_);
             if (lerr_) std::rethrow_exception(lerr_);
-            ljobs_.push_back(EntropyJob{prep_slot_, sse_ready});
+            ljobs_.push_back(EntropyJob{prep_slot_, sse_ready, es});
             slot_job_[prep_slot_] = ++l_pushed_;
         }
         lcv_.notify_all();
@@ -570,16 +566,12 @@ void GpuH264Encoder::enqueue_kernels(bool idr, const uint8_t* src_y, const uint8
     hipEvent_t sse_ready = nullptr;
     if (sl.deblock) {  // in-loop filter on the analysis stream: the next frame predicts from it,
                          // while this frame's CAVLC runs beside it on the entropy stream
-        unfiltered_planes(sl);
+        unfiltered_copy(sl);
         launch_deblock(geom_, sl.buf, src_y, src_uv, stream_);
         if (stream_e_) {
             HIP_CHECK(hipEventRecord(sl.deblock_done, stream_));
             sse_ready = sl.deblock_done;
         }
-    }
-    if (stream_a_ && hpel_side_ && publish) {  // the next picture's reference is final
-        HIP_CHECK(hipEventRecord(ref_ready_, stream_));
-        ref_seq_ = seq_;
     }
     launch_entropy(geom_, sl.buf, sl.host_out, es, sse_ready);
     HIP_CHECK(hipGetLastError());
@@ -607,8 +599,6 @@ void GpuH264Encoder::fill_state(FrameSlot& sl, bool idr, int qp, int ref, int cu
     f.pic_init_qp = common_.pic_init_qp();
     f.chroma_qp_offset = cfg_.chroma_qp_offset;
     f.log2_max_frame_num = common_.log2_max_frame_num();
-    const size_t org = (size_t)kHpelPad * hp_pitch_ + kHpelPad;
-    f.hp_pitch = hp_pitch_;
     f.aq = cfg_.aq;
     f.intra_in_p = cfg_.intra_in_p;
     f.partitions = cfg_.partitions ? 1 : 0;
@@ -616,14 +606,7 @@ void GpuH264Encoder::fill_state(FrameSlot& sl, bool idr, int qp, int ref, int cu
     f.mask_my0 = mask_mb_[1];
     f.mask_mx1 = mask_mb_[2];
     f.mask_my1 = mask_mb_[3];
-    f.hp_f = hp_[0] + org;
-    f.hp_h = hp_[1] + org;
-    f.hp_v = hp_[2] + org;
-    f.hp_j = hp_[3] + org;
-    f.me_f = sl.me_unf ? hpu_[0] + org : nullptr;
-    f.me_h = sl.me_unf ? hpu_[1] + org : nullptr;
-    f.me_v = sl.me_unf ? hpu_[2] + org : nullptr;
-    f.me_j = sl.me_unf ? hpu_[3] + org : nullptr;
+    f.me_ref = sl.me_unf ? rec_unf_ : nullptr;
     f.sse_part = sl.buf.sse_part;
     f.prev_src = src_keep_[ref];
     f.save_src = src_keep_[cur];

@@ -223,6 +223,9 @@ void emulation_prevent(std::vector<uint8_t>& out, const uint8_t* rbsp, size_t n)
 // (origin at (kHpelPad, kHpelPad), pitch in *hp_pitch).
 std::vector<std::vector<uint8_t>> hpel_planes_for_test(const uint8_t* ref, int coded_w, int coded_h, int pitch,
                                                        int* hp_pitch);
+// Test hook: the 16x16 luma prediction at quarter-sample position (x4, y4) of a host reference
+// picture (coded_h rows of `pitch` bytes), by k_inter_encode's interpolation; out: 256 bytes.
+void mc_luma_for_test(const uint8_t* ref, int coded_w, int coded_h, int pitch, int x4, int y4, uint8_t* out);
 
 class GpuH264Encoder final : public VideoEncoder {
    public:
@@ -243,7 +246,7 @@ class GpuH264Encoder final : public VideoEncoder {
     // Enqueue the encode of an NV12 frame already in device memory (pitch = pitch()).
     // Equivalent to prepare() + record_start() + enqueue_body() + record_done().  With
     // pipeline_depth 2 a second frame may be submitted before the first is collected:
-    // analysis (hpel/ME/inter or intra) runs on `stream`, entropy coding (CAVLC/scan/pack) on
+    // analysis (ME/inter or intra) runs on `stream`, entropy coding (CAVLC/scan/pack) on
     // an internal stream, so frame n's entropy coding overlaps frame n+1's analysis.
     void submit(const uint8_t* src_y, const uint8_t* src_uv, bool force_idr = false) override;
     // Wait for the oldest submitted frame and return its Annex-B access unit.
@@ -269,10 +272,9 @@ class GpuH264Encoder final : public VideoEncoder {
     void enqueue_analysis(bool idr, const uint8_t* src_y, const uint8_t* src_uv) override;
     void enqueue_entropy() override;
     void link_entropy() override;
-    void set_hpel_side_stream(bool on) override;
     void quiesce() override { drain_launcher(); }
-    // P pictures: the wait goes after k_hpel (which reads only the reference), so the
-    // interpolation of the new reference runs without waiting for the capture hand-off
+    // The wait goes directly before the picture's first kernel: on the queue it then follows the
+    // previous picture's analysis_done record without a kernel between the two barrier packets
     bool set_input_event(hipEvent_t ev) override {
         in_ev_ = ev;
         return true;
@@ -297,10 +299,9 @@ class GpuH264Encoder final : public VideoEncoder {
         FrameState* fs_host = nullptr;  // pinned
         uint8_t* host_out = nullptr;    // pinned, mapped: OutHeader | slice tables | payload
         hipEvent_t start = nullptr, analysis_done = nullptr, deblock_done = nullptr, done = nullptr;
-        hipEvent_t hpel_done = nullptr;
         bool idr = false;
         bool deblock = false;  // the picture's in-loop filter (decided when it is prepared)
-        bool me_unf = false;   // the reference was deblocked: the search uses its unfiltered planes (hpu_)
+        bool me_unf = false;   // the reference was deblocked: the search reads its unfiltered luma (rec_unf_)
         int qp = 0;
         uint64_t fidx = 0;     // picture number (seq_ when prepared)
         hipEvent_t me_done = nullptr;  // the side-stream motion search of this picture
@@ -308,7 +309,8 @@ class GpuH264Encoder final : public VideoEncoder {
     void alloc_slot(FrameSlot& sl);
     void free_slot(FrameSlot& sl);
     void fill_state(FrameSlot& sl, bool idr, int qp, int ref, int cur);
-    void unfiltered_planes(FrameSlot& sl);
+    void unfiltered_copy(FrameSlot& sl);
+    void ensure_me_stream();
     int probe_bytes(const uint8_t* src_y, const uint8_t* src_uv, int qp);
     // Entropy launcher (depth > 1, eager launches): a thread issues each frame's entropy chain --
     // the wait for its analysis, the CAVLC / scan / pack launches and its completion event, all
@@ -318,6 +320,7 @@ class GpuH264Encoder final : public VideoEncoder {
     struct EntropyJob {
         int slot;
         hipEvent_t sse_ready;
+        hipStream_t stream;  // the entropy stream of this picture
     };
     void launcher_loop();
     void wait_launched(int slot) const;  // the job that records slots_[slot].done was issued
@@ -337,16 +340,17 @@ class GpuH264Encoder final : public VideoEncoder {
     EncoderConfig cfg_;
     EncoderCommon common_;
     hipStream_t stream_;
-    hipStream_t stream_e_ = nullptr;  // entropy stream (depth 2)
-    // depth > 1, eager launches: k_hpel of a P picture runs on its own stream as soon as the
-    // reference is final (ref_ready_, recorded after the previous picture's last reconstruction
-    // kernel), beside the capture and colour conversion of the new picture, which it does not
-    // depend on; k_me_full waits for it (profiles/r04_h264)
-    hipStream_t stream_a_ = nullptr;
-    bool hpel_side_ = true;  // set_hpel_side_stream
+    hipStream_t stream_e_ = nullptr;  // entropy stream (depth >= 2)
+    // depth >= 3, eager launches: the launcher thread issues the entropy chains of odd pictures on a
+    // second stream -- every buffer a chain touches belongs to its frame slot, so two chains may run
+    // side by side; the done events and collect() stay in picture order.  Created with the first
+    // such picture, and drained and destroyed when stream_m_ appears: a session (analysis, capture,
+    // entropy, + one) stays within four streams, the number of hardware queues a process gets
+    // (a shared queue cost HEVC 28 %, profiles/r06_streams).
+    hipStream_t stream_e2_ = nullptr;
+    bool e2_retired_ = false;
     hipEvent_t in_ev_ = nullptr;  // set_input_event, consumed by the next analysis launch
-    hipEvent_t ref_ready_ = nullptr;
-    uint64_t seq_ = 0, ref_seq_ = ~0ull;  // pictures prepared; the one whose reconstruction ref_ready_ marks
+    uint64_t seq_ = 0;            // pictures prepared
     int depth_ = 1;
     Geometry geom_;
     FrameSlot slots_[kMaxInFlight];
@@ -355,16 +359,15 @@ class GpuH264Encoder final : public VideoEncoder {
     hipEvent_t last_done_ = nullptr;
     uint64_t last_t_end_ = 0;   // device clock at the end of the last collected frame
     double clock_khz_ = 100000;  // device wall-clock rate
-    uint8_t* hp_[4] = {nullptr, nullptr, nullptr, nullptr};  // padded F/H/V/J reference planes
-    // With the in-loop filter on, the motion search of picture n+1 reads the F/H/V/J planes of
-    // picture n's reconstruction before the filter (hpu_, k_hpel right after the reconstruction)
+    // With the in-loop filter on, the motion search of picture n+1 reads a copy of picture n's
+    // luma reconstruction from before the filter (rec_unf_, allocated only when the filter can run)
     // and runs on stream_m_ beside picture n's k_deblock; the analysis stream waits for it only
-    // before k_inter_encode (whose prediction uses the filtered planes hp_)
-    uint8_t* hpu_[4] = {nullptr, nullptr, nullptr, nullptr};
+    // before k_inter_encode (which predicts from the filtered picture).  stream_m_ is created
+    // when the first picture with a deblocked reference is prepared.
+    uint8_t* rec_unf_ = nullptr;
     hipStream_t stream_m_ = nullptr;
-    hipEvent_t ev_hpu_ = nullptr;  // hpu_ of the last deblocked picture written
+    hipEvent_t ev_hpu_ = nullptr;  // rec_unf_ of the last deblocked picture written
     bool last_deblock_ = false;    // the last prepared picture is deblocked
-    int hp_pitch_ = 0;
     uint8_t* rec_y_[2] = {nullptr, nullptr};
     uint8_t* rec_uv_[2] = {nullptr, nullptr};
     uint8_t* src_keep_[2] = {nullptr, nullptr};  // source luma of the last two frames (temporal AQ classes)

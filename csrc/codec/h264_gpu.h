@@ -1,8 +1,11 @@
 // Device data layout and host API of the HIP H.264 encoder.
 //
 // Per-frame kernel chain (all on one HIP stream, graph-capturable):
-//   P frame: k_hpel -> k_me_full -> k_inter_encode -> k_intra_analyze -> k_intra_wave
+//   P frame: k_me_full -> k_inter_encode -> k_intra_analyze -> k_intra_wave
 //            -> k_cavlc -> k_scan -> k_pack
+// Both P-frame kernels interpolate the reference's sub-sample positions themselves, from windows of
+// the reconstruction staged in LDS (the HEVC and VP8 encoders still build k_hpel's planes for
+// their prediction kernels).
 //   I frame: k_intra_analyze -> k_intra_wave -> k_cavlc -> k_scan -> k_pack
 // k_intra_analyze decides every macroblock's intra modes open-loop (SATD against predictions
 // from source neighbours, fully parallel); k_intra_wave reconstructs the intra macroblocks
@@ -85,7 +88,6 @@ struct FrameState {
     int32_t pic_init_qp;
     int32_t chroma_qp_offset;
     int32_t log2_max_frame_num;
-    int32_t hp_pitch;  // pitch of the padded half-pel planes
     int32_t aq;        // adaptive quantisation on/off (P frames)
     int32_t intra_in_p;  // P frames: k_intra_analyze / k_intra_wave run (distortion deltas included)
     int32_t partitions;  // P frames: k_me_full also searches 16x8 / 8x16 partitionings (H.264)
@@ -96,19 +98,11 @@ struct FrameState {
     // by k_inter_encode per MB, by a copy for IDR pictures); coded size, luma pitch
     const uint8_t* prev_src;
     uint8_t* save_src;
-    // padded reference planes (origin at picture (0,0), valid for x,y in [-kHpelPad, size+kHpelPad))
-    const uint8_t* hp_f;  // full-sample (edge-replicated)
-    const uint8_t* hp_h;  // horizontal half sample b at (x+1/2, y)
-    const uint8_t* hp_v;  // vertical half sample h at (x, y+1/2)
-    const uint8_t* hp_j;  // centre half sample j at (x+1/2, y+1/2)
-    // motion-search planes (k_me_full): the padded F / H / V / J planes of the reference picture's
-    // reconstruction BEFORE its in-loop filter when that picture was deblocked -- the next
-    // picture's search then depends only on the reconstruction, not on the filter, and runs beside
-    // it on another stream (profiles/r06_deblock) -- nullptr: the hp_* planes
-    const uint8_t* me_f;
-    const uint8_t* me_h;
-    const uint8_t* me_v;
-    const uint8_t* me_j;
+    // motion-search reference (k_me_full): the reference picture's luma BEFORE its in-loop filter
+    // when that picture was deblocked (pitch as ref_y) -- the next picture's search then depends
+    // only on the reconstruction, not on the filter, and runs beside it on another stream
+    // (profiles/r06_deblock) -- nullptr: ref_y
+    const uint8_t* me_ref;
     // distortion partials (Y, U, V, Y outside the mask MBs) over the display area, [4][kSsePartStride]: one per
     // inter workgroup / intra MB row, reduced by k_scan into OutHeader (no atomics)
     unsigned long long* sse_part;
@@ -179,22 +173,28 @@ struct DeviceBuffers {
 };
 
 // Kernel launchers (h264_kernels.hip).  All enqueue on `stream`; no host sync.
-// state: the frame state by value (the search runs on a side stream before the analysis stream's
-// first kernel has published it), or nullptr to read the published copy
+// The search is the first kernel of an H.264 P picture: with `publish` non-null it takes the state
+// by value, stores it to b.fs for the later kernels and stamps OutHeader::t_start; with nullptr it
+// reads b.fs (a memcpy node under hipGraph; the HEVC / VP8 encoders' own publication).
+// side: the launch goes to the side stream beside the reference's in-loop filter (k_me_full_val, the
+// same body under another name so that a kernel trace tells the two apart).
 void launch_me(const Geometry& g, const DeviceBuffers& b, const uint8_t* src_y, hipStream_t stream,
-               const FrameState* state = nullptr);
-// F / H / V / J planes of an explicit luma picture (the unfiltered reconstruction of a picture the
-// in-loop filter is about to modify), for the next picture's motion search (FrameState::me_*)
-void launch_hpel_of(const Geometry& g, const uint8_t* luma, uint8_t* const planes[4], int hp_pitch, hipStream_t stream);
+               const FrameState* publish = nullptr, bool side = false);
+// Copy of a luma picture (the unfiltered reconstruction of a picture the in-loop filter is about to
+// modify) for the next picture's motion search (FrameState::me_ref)
+void launch_copy_luma(const Geometry& g, const uint8_t* luma, uint8_t* dst, hipStream_t stream);
+// Test hook: the 16x16 quarter-sample luma prediction at (x4, y4) (quarter samples, any position)
+// from a reference picture on the device, by k_inter_encode's interpolation; out: 256 bytes
+void launch_mc_luma_test(const Geometry& g, const uint8_t* ref, int x4, int y4, uint8_t* out, hipStream_t stream);
 void launch_inter(const Geometry& g, const DeviceBuffers& b, const uint8_t* src_y, const uint8_t* src_uv,
                   hipStream_t stream);
-// The first kernel of a frame (launch_intra for I, launch_hpel for P) publishes the frame
+// The first kernel of a frame (launch_intra for I, launch_me for P) publishes the frame
 // state: with `publish` non-null it takes the state by value and stores it to b.fs for the
 // later kernels (no copy node); with nullptr it reads b.fs (filled by a memcpy node, hipGraph).
 void launch_intra(const Geometry& g, const DeviceBuffers& b, const uint8_t* src_y, const uint8_t* src_uv,
                   hipStream_t stream, const FrameState* publish = nullptr);
 // Build the padded F/H/V/J planes of the reference luma (b.fs->ref_y) into `planes` (4 planes,
-// each hp_pitch x (coded_h + 2*kHpelPad), origin offset applied by the caller via FrameState).
+// each hp_pitch x (coded_h + 2*kHpelPad)); HEVC and VP8 prediction, not used by H.264 pictures.
 void launch_hpel(const Geometry& g, const DeviceBuffers& b, uint8_t* const planes[4], int hp_pitch,
                  hipStream_t stream, const FrameState* publish = nullptr);
 // In-loop deblocking of the reconstruction (FrameState::rec_y / rec_uv, in place) + the distortion

@@ -102,42 +102,6 @@ __device__ __forceinline__ int wave_sum(int v) {
 }
 
 // ------------------------------------------------------------------ half-pel planes
-struct Planes {
-    const uint8_t *f, *h, *v, *j;
-    int pitch;
-};
-__device__ __forceinline__ Planes planes_of(const FrameState* fs) {
-    return Planes{fs->hp_f, fs->hp_h, fs->hp_v, fs->hp_j, fs->hp_pitch};
-}
-// the motion search's planes (FrameState::me_*: the reference's unfiltered reconstruction)
-__device__ __forceinline__ Planes me_planes_of(const FrameState* fs) {
-    return fs->me_f ? Planes{fs->me_f, fs->me_h, fs->me_v, fs->me_j, fs->hp_pitch} : planes_of(fs);
-}
-// Quarter-sample luma value from the precomputed planes (Table 8-12); identical to
-// luma_qpel() on the clamped reference.
-__device__ __forceinline__ int qpel_planes(const Planes& P, int x4, int y4) {
-    const int xi = x4 >> 2, yi = y4 >> 2, xf = x4 & 3, yf = y4 & 3;
-    const int o = yi * P.pitch + xi;
-    const int G = P.f[o];
-    if ((xf | yf) == 0) return G;
-    if (yf == 0) {
-        const int b = P.h[o];
-        if (xf == 2) return b;
-        return ((xf == 1 ? G : (int)P.f[o + 1]) + b + 1) >> 1;
-    }
-    if (xf == 0) {
-        const int hh = P.v[o];
-        if (yf == 2) return hh;
-        return ((yf == 1 ? G : (int)P.f[o + P.pitch]) + hh + 1) >> 1;
-    }
-    if (xf == 2 && yf == 2) return P.j[o];
-    if (xf == 2) return ((yf == 1 ? (int)P.h[o] : (int)P.h[o + P.pitch]) + P.j[o] + 1) >> 1;
-    if (yf == 2) return ((xf == 1 ? (int)P.v[o] : (int)P.v[o + 1]) + P.j[o] + 1) >> 1;
-    const int bb = (yf == 1) ? P.h[o] : P.h[o + P.pitch];
-    const int hh = (xf == 1) ? P.v[o] : P.v[o + 1];
-    return (bb + hh + 1) >> 1;
-}
-
 // LDS-tiled F/H/V/J plane builder, 128x16 output tile per 256-thread workgroup.
 //  1. the (16+5)-row clamped sample footprint is staged as whole dwords (aligned start
 //     4 samples left of the tile; interior tiles use dword loads, border tiles clamp);
@@ -179,12 +143,11 @@ __device__ __forceinline__ const FrameState& state_of(const StateArg& a) { retur
 
 __global__ __launch_bounds__(256) void k_hpel(Geometry g, StateArg sa, uint8_t* __restrict__ pf,
                                               uint8_t* __restrict__ ph, uint8_t* __restrict__ pv,
-                                              uint8_t* __restrict__ pj, int hp_pitch,
-                                              const uint8_t* __restrict__ src) {
+                                              uint8_t* __restrict__ pj, int hp_pitch) {
     __shared__ uint32_t smp[kHpTH + 5][kHpSW / 4];
     __shared__ int4 b1[kHpTH + 5][kHpTW / 4];  // 4 columns per entry
     publish_state(sa);
-    const uint8_t* __restrict__ ref = src ? src : state_of(sa).ref_y;  // src: an explicit picture
+    const uint8_t* __restrict__ ref = state_of(sa).ref_y;
     const int px0 = blockIdx.x * kHpTW, py0 = blockIdx.y * kHpTH;  // padded-plane coordinates
     const int W = g.coded_w + 2 * kHpelPad, H = g.coded_h + 2 * kHpelPad;
     const int tid = threadIdx.x;
@@ -262,7 +225,7 @@ __global__ __launch_bounds__(256) void k_hpel(Geometry g, StateArg sa, uint8_t* 
 
 // Quarter-sample luma value from an LDS-staged 18x18 footprint of the four planes
 // (sp[0] F, sp[1] H, sp[2] V, sp[3] J; local origin one sample up-left of the integer
-// match); exactly qpel_planes() on the same samples.
+// match); Table 8-12 on k_hpel's planes, identical to luma_qpel() on the clamped reference.
 constexpr int kSpW = 20;
 __device__ __forceinline__ int qpel_lds(const uint8_t (*sp)[18][kSpW], int x4, int y4) {
     const int xi = x4 >> 2, yi = y4 >> 2, xf = x4 & 3, yf = y4 & 3;
@@ -288,16 +251,60 @@ __device__ __forceinline__ int qpel_lds(const uint8_t (*sp)[18][kSpW], int x4, i
 
 // ------------------------------------------------------------------ motion estimation
 constexpr int kMaxRange = 32;
-static_assert(kMaxRange + 2 <= kHpelPad, "search window must stay inside the padded planes");
-constexpr int kWinStride = 16 + 2 * kMaxRange + 8;  // bytes per LDS window row (dword padded)
+// The LDS search window holds the edge-clamped reference around the macroblock: the +-R candidate
+// positions plus the reach of the six-tap filter around the +-1-sample sub-sample refinement, 3
+// samples before and 4 after on each axis (4 before in x: whole dwords).  Window byte (wx, wy) is
+// picture sample (x0 - R - kWinPadX + wx, y0 - R - kWinPadY + wy).
+constexpr int kWinPadX = 4, kWinPadY = 3;
+constexpr int kWinStride = 16 + 2 * kMaxRange + 8;  // bytes per LDS window row: a full row at R = 32
+constexpr int kWinRows = 16 + 2 * kMaxRange + 7;
+
+constexpr int kMeThreads = 256, kMeWaves = kMeThreads / 64;
+// F / H / V / J footprints (18x18 each, the layout qpel_lds reads) around `n` (1 or 2) integer
+// matches, computed from the staged window with k_hpel's arithmetic: unclipped horizontal six-tap
+// intermediates b1, H = (b1 + 16) >> 5, V the same from the sample column, J = (six taps over
+// the b1 column + 512) >> 10.  org0 / org1: window byte of each footprint's sample (0, 0), one
+// sample up-left of the match; its 2 rows / columns before and 3 after are in the window.  The
+// whole workgroup calls it (one barrier inside) and synchronises before it reads sp.
+constexpr int kFpRows = 18 + 5;
+__device__ __forceinline__ void build_footprints(const uint8_t* win, int org0, int org1, int n,
+                                                 uint8_t (*sp)[4][18][kSpW], int16_t (*b1)[kFpRows][kSpW], int tid) {
+    for (int i = tid; i < n * kFpRows * 18; i += kMeThreads) {
+        const int pi = i / (kFpRows * 18), rem = i - pi * (kFpRows * 18), r = rem / 18, c = rem - r * 18;
+        const uint8_t* p = win + (pi ? org1 : org0) + (r - 2) * kWinStride + c;
+        b1[pi][r][c] = (int16_t)tap6(p[-2], p[-1], p[0], p[1], p[2], p[3]);  // -2550 .. 10710
+    }
+    __syncthreads();
+    for (int i = tid; i < n * 324; i += kMeThreads) {
+        const int pi = i / 324, rem = i - pi * 324, r = rem / 18, c = rem - r * 18;
+        const uint8_t* p = win + (pi ? org1 : org0) + r * kWinStride + c;
+        const int16_t(*b)[kSpW] = b1[pi];
+        const int v1 = tap6(p[-2 * kWinStride], p[-kWinStride], p[0], p[kWinStride], p[2 * kWinStride], p[3 * kWinStride]);
+        const int j1 = tap6(b[r][c], b[r + 1][c], b[r + 2][c], b[r + 3][c], b[r + 4][c], b[r + 5][c]);
+        sp[pi][0][r][c] = p[0];
+        sp[pi][1][r][c] = (uint8_t)clip255((b[r + 2][c] + 16) >> 5);
+        sp[pi][2][r][c] = (uint8_t)clip255((v1 + 16) >> 5);
+        sp[pi][3][r][c] = (uint8_t)clip255((j1 + 512) >> 10);
+    }
+}
 
 // Four waves.  (Five -- the +-16 search's 297 candidate tasks in one pass of 320 threads instead
 // of 1.16 passes of 256 -- measured slower: 45 -> 54 us at 1080p, 78 -> 110 us at 4K, the larger
 // workgroups costing more in occupancy than the shorter second pass saved: profiles/r04_h264.)
-constexpr int kMeThreads = 256, kMeWaves = kMeThreads / 64;
-__device__ __forceinline__ void me_full_body(const Geometry& g, const FrameState* __restrict__ fs,
-                                             const uint8_t* __restrict__ src_y, MbInfo* __restrict__ mbs) {
-    __shared__ uint32_t win32[(16 + 2 * kMaxRange) * kWinStride / 4];
+// What the search reads of the frame state, taken once into scalar registers (a pointer that is
+// either the kernel's argument block or the published copy would turn every read into a flat load)
+struct MeState {
+    const uint8_t* ref;  // the reference picture's luma, before its in-loop filter when it was deblocked
+    int qp, search_range, subpel, me_coarse, partitions;
+};
+__device__ __forceinline__ MeState me_state(const FrameState& f) {
+    return MeState{f.me_ref ? f.me_ref : f.ref_y, f.qp, f.search_range, f.subpel, f.me_coarse, f.partitions};
+}
+__device__ __forceinline__ void me_full_body(const Geometry& g, const MeState& st, const uint8_t* __restrict__ src_y,
+                                             MbInfo* __restrict__ mbs) {
+    __shared__ uint32_t win_lds[kWinRows * kWinStride / 4];
+    __shared__ uint8_t sp2[2][4][18][kSpW];   // sub-sample footprints: the 16x16 match, or two partitions
+    __shared__ int16_t fp_b1[2][kFpRows][kSpW];
     __shared__ uint32_t srcw[64];
     __shared__ unsigned long long red[kMeWaves];
     __shared__ uint32_t cand_cost[8];
@@ -307,10 +314,10 @@ __device__ __forceinline__ void me_full_body(const Geometry& g, const FrameState
     const int mbx = mbi % g.mb_w, mby = mbi / g.mb_w;
     const int x0 = mbx * 16, y0 = mby * 16;
     const int tid = threadIdx.x, lane = tid & 63;
-    const int R = me_range(fs->search_range);
+    const int R = me_range(st.search_range);
     const int W = 16 + 2 * R;
-    const Planes P = me_planes_of(fs);  // the unfiltered reference when it was deblocked
-    const int lambda = lambda_sad(fs->qp);
+    const uint8_t* __restrict__ ref = st.ref;
+    const int lambda = lambda_sad(st.qp);
 
     // static-block early exit first: SAD of the zero vector from one source and one reference
     // pixel per thread (same rule as the CPU encoder), so the ~70 % static MBs of a desktop
@@ -321,13 +328,13 @@ __device__ __forceinline__ void me_full_body(const Geometry& g, const FrameState
         if (tid < 64) {  // one wave: a dword of source and reference per lane, v_sad_u8
             const int r = tid >> 2, c4 = (tid & 3) * 4;
             const uint32_t sw = *reinterpret_cast<const uint32_t*>(src_y + (y0 + r) * g.pitch + x0 + c4);
-            const uint32_t rw = *reinterpret_cast<const uint32_t*>(P.f + (y0 + r) * P.pitch + x0 + c4);
+            const uint32_t rw = *reinterpret_cast<const uint32_t*>(ref + (y0 + r) * g.pitch + x0 + c4);
             const int d = wave_sum((int)__builtin_amdgcn_sad_u8(sw, rw, 0u));
             if (tid == 0) s_sad0[0] = (uint32_t)d;
         }
         __syncthreads();
         const uint32_t sad0 = s_sad0[0];
-        if (sad0 <= static_sad(fs->qp)) {
+        if (sad0 <= static_sad(st.qp)) {
             if (tid == 0) {
                 MbInfo& m = mbs[mbi];
                 m.mvx = 0;
@@ -338,13 +345,35 @@ __device__ __forceinline__ void me_full_body(const Geometry& g, const FrameState
             return;  // uniform across the workgroup
         }
     }
-    // search window from the padded full-sample plane with dword loads (x0 - R is a
-    // multiple of 4 and R + 2 <= kHpelPad: no clamping, no byte gathers)
+    // search window straight from the reference picture, edge-clamped.  Its left edge x0 - R - 4 is
+    // a multiple of 4 and so is the coded width: a window dword lies wholly inside a picture row
+    // (one dword load) or wholly beside it (the row's edge sample four times) -- no byte gathers.
     const bool t256 = tid < 256;  // the threads of the 256-thread refinement layouts
-    for (int i = tid; i < W * kWs4; i += kMeThreads) {
+    const int wrows = W + 2 * kWinPadY + 1, wx0 = x0 - R - kWinPadX, wy0 = y0 - R - kWinPadY;
+    const bool dwords = (g.pitch & 3) == 0 && (reinterpret_cast<uintptr_t>(ref) & 3) == 0;
+    for (int i = tid; i < wrows * kWs4; i += kMeThreads) {
         const int wy = i / kWs4, wx4 = (i - wy * kWs4) * 4;
-        win32[i] = (wx4 < W) ? *reinterpret_cast<const uint32_t*>(P.f + (y0 - R + wy) * P.pitch + (x0 - R + wx4)) : 0u;
+        uint32_t w = 0u;
+        if (wx4 < W + 2 * kWinPadX) {
+            const int py = min(max(wy0 + wy, 0), g.coded_h - 1), px = wx0 + wx4;
+            const uint8_t* row = ref + (size_t)py * g.pitch;
+            if (px < 0)
+                w = row[0] * 0x01010101u;
+            else if (px >= g.coded_w)
+                w = row[g.coded_w - 1] * 0x01010101u;
+            else if (dwords)
+                w = *reinterpret_cast<const uint32_t*>(row + px);
+            else
+                w = row[px] | ((uint32_t)row[px + 1] << 8) | ((uint32_t)row[px + 2] << 16) | ((uint32_t)row[px + 3] << 24);
+        }
+        win_lds[i] = w;
     }
+    // the search addresses the window from its first candidate position (vector (-R, -R))
+    const uint32_t* win32 = win_lds + kWinPadY * kWs4 + kWinPadX / 4;
+    // window byte (in win_lds) one sample up-left of the integer match (vx, vy): build_footprints
+    auto fp_org = [&](int vx, int vy) {
+        return ((vy >> 2) + R + kWinPadY - 1) * kWinStride + (vx >> 2) + R + kWinPadX - 1;
+    };
     if (tid < 64) {
         const int r = tid >> 2, c = (tid & 3) * 4;
         srcw[tid] = *reinterpret_cast<const uint32_t*>(src_y + (y0 + r) * g.pitch + x0 + c);
@@ -356,11 +385,11 @@ __device__ __forceinline__ void me_full_body(const Geometry& g, const FrameState
     // (instead of 5 per candidate), 12 v_alignbyte and 16 v_sad_u8.
     const int side = 2 * R + 1, gw = (side + 3) >> 2, ngroups = side * gw;
     unsigned long long best = ~0ull;
-    const bool coarse = fs->me_coarse != 0;
+    const bool coarse = st.me_coarse != 0;
     // coarse mode (me_coarse): the even-offset grid first -- two candidates per thread (window
     // shifts 0 and 2 of a dword group), (R + 1) * gw tasks in one pass -- then the 8 integer
     // neighbours of its best (me_search_cpu does the same)
-    const bool parts = fs->partitions != 0;  // 16x8 / 8x16 partitionings searched too (me_search_parts_cpu)
+    const bool parts = st.partitions != 0;  // 16x8 / 8x16 partitionings searched too (me_search_parts_cpu)
     const int ntask = (coarse && !parts) ? (R + 1) * gw : 0;
     auto mkey = [&](uint32_t sad, int dxr, int dyr) {
         const int dx = dxr - R, dy = dyr - R;
@@ -580,18 +609,13 @@ __device__ __forceinline__ void me_full_body(const Geometry& g, const FrameState
                 pvy[i] = 4 * ((cb / side) - R);
                 pcost[i] = (uint32_t)(pbest[s0 + i] >> 32);
             }
-            if (fs->subpel) {
+            if (st.subpel) {
                 // half then quarter pel per partition over its own rectangle: an 18x18 footprint
                 // per partition, 16 lanes (8 samples each) per candidate, both partitions at once
-                __shared__ uint8_t psp[2][4][18][kSpW];
+                uint8_t(*psp)[4][18][kSpW] = sp2;
                 __shared__ uint32_t pcand[2][8];
-                for (int i = tid; i < 2 * 4 * 18 * 18; i += kMeThreads) {
-                    const int pi = i / (4 * 324), rem0 = i - pi * 4 * 324;
-                    const int pl = rem0 / 324, rem = rem0 - pl * 324, r = rem / 18, c = rem - r * 18;
-                    const uint8_t* base = pl == 0 ? P.f : pl == 1 ? P.h : pl == 2 ? P.v : P.j;
-                    const int ix = x0 + (pvx[pi] >> 2) - 1, iy = y0 + (pvy[pi] >> 2) - 1;
-                    psp[pi][pl][r][c] = base[(iy + r) * P.pitch + ix + c];
-                }
+                build_footprints(reinterpret_cast<const uint8_t*>(win_lds), fp_org(pvx[0], pvy[0]),
+                                 fp_org(pvx[1], pvy[1]), 2, sp2, fp_b1, tid);
                 __syncthreads();
                 const int pi = (tid & 255) >> 7, k = (tid >> 4) & 7, sub = tid & 15;
                 // the 8 samples of this lane inside the partition rectangle
@@ -648,19 +672,14 @@ __device__ __forceinline__ void me_full_body(const Geometry& g, const FrameState
         }
     }
 
-    if (fs->subpel) {
+    if (st.subpel) {
         // half-pel then quarter-pel around the integer match.  Every candidate of both steps
-        // lies in one 18x18 footprint of the F/H/V/J planes (the integer match +-1 sample),
-        // staged into LDS once with independent byte loads; the 8 neighbours of a step are
+        // lies in one 18x18 footprint of the F/H/V/J samples (the integer match +-1 sample),
+        // interpolated once from the staged window; the 8 neighbours of a step are
         // scored at once, one per 32-lane half-wave group (8 pixels per lane, source from
         // srcw), a 5-step xor shuffle reduces each group, one barrier publishes the costs.
-        __shared__ uint8_t sp[4][18][kSpW];
-        const int ix = x0 + (mvx >> 2) - 1, iy = y0 + (mvy >> 2) - 1;
-        for (int i = tid; i < 4 * 18 * 18; i += kMeThreads) {
-            const int pl = i / 324, rem = i - pl * 324, r = rem / 18, c = rem - r * 18;
-            const uint8_t* base = pl == 0 ? P.f : pl == 1 ? P.h : pl == 2 ? P.v : P.j;
-            sp[pl][r][c] = base[(iy + r) * P.pitch + ix + c];
-        }
+        uint8_t(*sp)[18][kSpW] = sp2[0];
+        build_footprints(reinterpret_cast<const uint8_t*>(win_lds), fp_org(mvx, mvy), 0, 1, sp2, fp_b1, tid);
         __syncthreads();
         uint32_t cur_cost = (uint32_t)(b >> 32);
         const int k = (tid & 255) >> 5, sub = tid & 31;
@@ -707,16 +726,19 @@ __device__ __forceinline__ void me_full_body(const Geometry& g, const FrameState
     }
 }
 
-// The search reads the published frame state (the analysis stream's first kernel wrote it) or,
-// on the side stream beside the previous picture's in-loop filter, a copy passed by value
-// (a separate kernel, so the common launch keeps its small argument block)
-__global__ __launch_bounds__(kMeThreads) void k_me_full(Geometry g, const FrameState* __restrict__ fs,
-                                                  const uint8_t* __restrict__ src_y, MbInfo* __restrict__ mbs) {
-    me_full_body(g, fs, src_y, mbs);
+// The search is the first kernel of an H.264 P picture: it publishes the frame state for the later
+// kernels and stamps the start (StateArg), or reads the published copy (hipGraph, HEVC, VP8).
+// k_me_full_val is the launch on the side stream beside the previous picture's in-loop filter:
+// the same body, always with the state by value (a name of its own in kernel traces).
+__global__ __launch_bounds__(kMeThreads) void k_me_full(Geometry g, StateArg sa, const uint8_t* __restrict__ src_y,
+                                                        MbInfo* __restrict__ mbs) {
+    publish_state(sa);
+    me_full_body(g, sa.publish ? me_state(sa.v) : me_state(*sa.dst), src_y, mbs);
 }
-__global__ __launch_bounds__(kMeThreads) void k_me_full_val(Geometry g, FrameState fs,
-                                                      const uint8_t* __restrict__ src_y, MbInfo* __restrict__ mbs) {
-    me_full_body(g, &fs, src_y, mbs);
+__global__ __launch_bounds__(kMeThreads) void k_me_full_val(Geometry g, StateArg sa, const uint8_t* __restrict__ src_y,
+                                                            MbInfo* __restrict__ mbs) {
+    publish_state(sa);
+    me_full_body(g, me_state(sa.v), src_y, mbs);
 }
 
 // ------------------------------------------------------------------ inter encode
@@ -794,6 +816,105 @@ __device__ __forceinline__ void dequant_row(const int* z, int r, int qp, int* d)
     for (int c = 0; c < 4; ++c) d[c] = z[c] * kDequantV[qm][kPosClass[r * 4 + c]] * (1 << qs);
 }
 
+__device__ __forceinline__ void wave_sync_lds() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// Quarter-sample luma prediction of one macroblock straight from the reference picture (8.4.2.2.1;
+// sample for sample luma_qpel() of the CPU encoder), by one wave.  The macroblock has n = 1 or 2
+// vectors (partitions); (xa, ya) and (xb, yb) are the quarter-sample positions its top-left sample
+// is predicted from under each.  The wave stages, per vector, the edge-clamped (16+5) x (16+5)
+// sample window of the whole block -- reference sample (bx - 2 + c, by - 2 + r) at byte c of row r,
+// rows of kMcStride bytes -- in LDS, both windows in one round of loads; then every lane
+// interpolates its four samples (c0 .. c0+3, r), c0 a multiple of 4, under vector lpi from the
+// 6 x 9 samples around them, into one dword (*out, first sample in the low byte).
+constexpr int kMcStride = 24, kMcRows = 16 + 5, kMcWords = kMcRows * kMcStride / 4;
+__device__ __forceinline__ void mc_luma_wave(uint32_t* __restrict__ w, const uint8_t* __restrict__ ref, int pitch,
+                                             int cw, int ch, int n, int xa, int ya, int xb, int yb, int lane, int lpi,
+                                             uint32_t* out) {
+    const bool aligned = (pitch & 3) == 0 && (reinterpret_cast<uintptr_t>(ref) & 3) == 0;
+    for (int i = lane; i < n * kMcWords; i += 64) {
+        const int pi = i >= kMcWords ? 1 : 0, j = i - pi * kMcWords;
+        const int wr = j / (kMcStride / 4), q = j - wr * (kMcStride / 4);
+        const int xs = ((pi ? xb : xa) >> 2) - 2, ys = ((pi ? yb : ya) >> 2) - 2;
+        uint32_t v;
+        // rows wholly inside the picture's columns: a window dword from two aligned dwords of the row
+        if (aligned && xs >= 0 && (xs & ~3) + kMcStride + 4 <= cw) {
+            const int py = min(max(ys + wr, 0), ch - 1), px = xs + 4 * q;
+            const uint32_t* qa = reinterpret_cast<const uint32_t*>(ref + (size_t)py * pitch + (px & ~3));
+            const uint32_t sh = (uint32_t)(px & 3);
+            v = sh ? __builtin_amdgcn_alignbyte(qa[1], qa[0], sh) : qa[0];
+        } else {
+            v = 0;
+            for (int k = 0; k < 4; ++k) v |= (uint32_t)ref_px(ref, pitch, cw, ch, xs + 4 * q + k, ys + wr) << (8 * k);
+        }
+        w[i] = v;
+    }
+    wave_sync_lds();
+    {
+        const int xf = (lpi ? xb : xa) & 3, yf = (lpi ? yb : ya) & 3;
+        w += lpi * kMcWords;
+        const int r = lane >> 2, q0 = lane & 3;
+        // window rows r .. r+5, bytes c0 .. c0+8 as three dwords a row; after every sample the rows
+        // move one byte down, so the current sample is always s(2, 2) and the loop stays rolled
+        // (18 live registers and one copy of the code, not 54 and four)
+        uint32_t wd[6][3];
+#pragma unroll
+        for (int rr = 0; rr < 6; ++rr) {
+            const uint32_t* row = w + (r + rr) * (kMcStride / 4) + q0;
+            wd[rr][0] = row[0];
+            wd[rr][1] = row[1];
+            wd[rr][2] = row[2];
+        }
+        auto s = [&](int rr, int c) { return byte_of(wd[rr][c >> 2], c & 3); };
+        auto b1 = [&](int rr) { return tap6(s(rr, 0), s(rr, 1), s(rr, 2), s(rr, 3), s(rr, 4), s(rr, 5)); };
+        auto v1 = [&](int c) { return tap6(s(0, c), s(1, c), s(2, c), s(3, c), s(4, c), s(5, c)); };
+        auto b_at = [&](int rr) { return clip255((b1(rr) + 16) >> 5); };  // b at (x+1/2, row)
+        auto h_at = [&](int c) { return clip255((v1(c) + 16) >> 5); };    // h at (column, y+1/2)
+        auto j_val = [&]() { return clip255((tap6(b1(0), b1(1), b1(2), b1(3), b1(4), b1(5)) + 512) >> 10); };
+        uint32_t packed = 0;
+#pragma unroll 1
+        for (int k = 0; k < 4; ++k) {
+            const int G = s(2, 2);
+            int p;
+            if ((xf | yf) == 0)
+                p = G;
+            else if (yf == 0)
+                p = xf == 2 ? b_at(2) : ((xf == 1 ? G : s(2, 3)) + b_at(2) + 1) >> 1;
+            else if (xf == 0)
+                p = yf == 2 ? h_at(2) : ((yf == 1 ? G : s(3, 2)) + h_at(2) + 1) >> 1;
+            else if (xf == 2 && yf == 2)
+                p = j_val();
+            else if (xf == 2)
+                p = ((yf == 1 ? b_at(2) : b_at(3)) + j_val() + 1) >> 1;
+            else if (yf == 2)
+                p = ((xf == 1 ? h_at(2) : h_at(3)) + j_val() + 1) >> 1;
+            else
+                p = ((yf == 1 ? b_at(2) : b_at(3)) + (xf == 1 ? h_at(2) : h_at(3)) + 1) >> 1;
+            packed |= (uint32_t)p << (8 * k);
+#pragma unroll
+            for (int rr = 0; rr < 6; ++rr) {
+                wd[rr][0] = __builtin_amdgcn_alignbyte(wd[rr][1], wd[rr][0], 1);
+                wd[rr][1] = __builtin_amdgcn_alignbyte(wd[rr][2], wd[rr][1], 1);
+                wd[rr][2] >>= 8;
+            }
+        }
+        *out = packed;
+    }
+}
+
+// Test hook: one block by mc_luma_wave.
+__global__ __launch_bounds__(64) void k_mc_luma_test(Geometry g, const uint8_t* __restrict__ ref, int x4, int y4,
+                                                     uint8_t* __restrict__ out) {
+    __shared__ uint32_t w[kMcWords];
+    const int lane = threadIdx.x;
+    uint32_t p = 0;
+    mc_luma_wave(w, ref, g.pitch, g.coded_w, g.coded_h, 1, x4, y4, x4, y4, lane, 0, &p);
+    reinterpret_cast<uint32_t*>(out)[lane] = p;  // lane = 4 * row + dword of the row
+}
+
 __global__ __launch_bounds__(256) void k_inter_encode(Geometry g, const FrameState* __restrict__ fs,
                                                        const uint8_t* __restrict__ src_y,
                                                        const uint8_t* __restrict__ src_uv, MbInfo* __restrict__ mbs,
@@ -801,6 +922,7 @@ __global__ __launch_bounds__(256) void k_inter_encode(Geometry g, const FrameSta
                                                        int* __restrict__ wave_prog) {
     __shared__ uint8_t pred[4][384];
     __shared__ int16_t res[4][384];
+    __shared__ uint32_t mcw[4][2 * kMcWords];  // per wave: the windows of fractional vectors' prediction
     __shared__ int cdc[4][8];
     __shared__ int cdc_nz[4][2];
 
@@ -812,7 +934,8 @@ __global__ __launch_bounds__(256) void k_inter_encode(Geometry g, const FrameSta
     const bool valid = mbi < nmb;
     const int mbx = valid ? mbi % g.mb_w : 0, mby = valid ? mbi / g.mb_w : 0;
     const int x0 = mbx * 16, y0 = mby * 16;
-    const Planes P = planes_of(fs);
+    const uint8_t* __restrict__ ref_y = fs->ref_y;
+    const bool ref_dwords = (g.pitch & 3) == 0 && (reinterpret_cast<uintptr_t>(ref_y) & 3) == 0;
     const uint8_t* ref_uv = fs->ref_uv;
     const int cw = g.coded_w / 2, ch = g.coded_h / 2;
     int mvx = 0, mvy = 0;
@@ -847,28 +970,37 @@ __global__ __launch_bounds__(256) void k_inter_encode(Geometry g, const FrameSta
             }
             *reinterpret_cast<uint32_t*>(fs->save_src + (y0 + r) * g.pitch + x0 + c0) = sw;
         }
-        if (((mvx | mvy) & 3) == 0) {
-            // full-sample vector (static desktop, scrolled text): the 4 predictions are 4 bytes of the
-            // padded full-sample plane, from two aligned dwords instead of 4 byte gathers
-            const uint8_t* q = P.f + (size_t)((y0 + r) + (mvy >> 2)) * P.pitch + (x0 + c0 + (mvx >> 2));
-            const uint32_t* qa = reinterpret_cast<const uint32_t*>(reinterpret_cast<uintptr_t>(q) & ~(uintptr_t)3);
-            const uint32_t sh = (uint32_t)(reinterpret_cast<uintptr_t>(q) & 3);
-            const uint32_t pw = sh ? __builtin_amdgcn_alignbyte(qa[1], qa[0], sh) : qa[0];
-            for (int k = 0; k < 4; ++k) {
-                const int p = (int)((pw >> (8 * k)) & 0xff);
-                const int d = (int)((sw >> (8 * k)) & 0xff) - p;
-                pred[wave][r * 16 + c0 + k] = (uint8_t)p;
-                res[wave][r * 16 + c0 + k] = (int16_t)d;
-                lsad += d < 0 ? -d : d;
-            }
+        // luma prediction from the reference picture; the macroblock's one or two vectors are
+        // uniform across the wave (the lane's 4 samples lie in partition lpi: vector (mvx, mvy))
+        const int part = __builtin_amdgcn_readfirstlane((int)mi.part);
+        const Mv va = blk_mv(mi, 0, 0), vb = blk_mv(mi, part == kPart8x16 ? 2 : 0, part == kPart16x8 ? 2 : 0);
+        const int vax = __builtin_amdgcn_readfirstlane(va.x), vay = __builtin_amdgcn_readfirstlane(va.y);
+        const int vbx = __builtin_amdgcn_readfirstlane(vb.x), vby = __builtin_amdgcn_readfirstlane(vb.y);
+        uint32_t pw = 0;  // the lane's 4 predicted samples
+        if ((vax | vay | vbx | vby) & 3) {
+            // a fractional vector: interpolated from the block's window(s) staged in LDS
+            const int lpi = part == kPart16x8 ? (r >> 3) : (part == kPart8x16 ? (c0 >> 3) : 0);
+            mc_luma_wave(mcw[wave], ref_y, g.pitch, g.coded_w, g.coded_h, part == kPart16x16 ? 1 : 2, x0 * 4 + vax,
+                         y0 * 4 + vay, x0 * 4 + vbx, y0 * 4 + vby, lane, lpi, &pw);
         } else {
-            for (int k = 0; k < 4; ++k) {
-                const int p = qpel_planes(P, (x0 + c0 + k) * 4 + mvx, (y0 + r) * 4 + mvy);
-                const int d = (int)((sw >> (8 * k)) & 0xff) - p;
-                pred[wave][r * 16 + c0 + k] = (uint8_t)p;
-                res[wave][r * 16 + c0 + k] = (int16_t)d;
-                lsad += d < 0 ? -d : d;
+            // full-sample vectors (static desktop, scrolled text): 4 bytes of the reference row (edge
+            // clamped), inside the picture from two aligned dwords instead of 4 byte gathers
+            const int px = x0 + c0 + (mvx >> 2), py = min(max(y0 + r + (mvy >> 2), 0), g.coded_h - 1);
+            if (px >= 0 && px + 4 <= g.coded_w && ((px & 3) == 0 || (px & ~3) + 8 <= g.pitch) && ref_dwords) {
+                const uint32_t* qa = reinterpret_cast<const uint32_t*>(ref_y + (size_t)py * g.pitch + (px & ~3));
+                const uint32_t sh = (uint32_t)(px & 3);
+                pw = sh ? __builtin_amdgcn_alignbyte(qa[1], qa[0], sh) : qa[0];
+            } else {
+                for (int k = 0; k < 4; ++k)
+                    pw |= (uint32_t)ref_px(ref_y, g.pitch, g.coded_w, g.coded_h, px + k, py) << (8 * k);
             }
+        }
+        for (int k = 0; k < 4; ++k) {
+            const int p = (int)((pw >> (8 * k)) & 0xff);
+            const int d = (int)((sw >> (8 * k)) & 0xff) - p;
+            pred[wave][r * 16 + c0 + k] = (uint8_t)p;
+            res[wave][r * 16 + c0 + k] = (int16_t)d;
+            lsad += d < 0 ? -d : d;
         }
         const int cr_ = lane >> 3, cc = lane & 7;
         const int xc = x0 / 2 + cc, yc = y0 / 2 + cr_;
@@ -1026,11 +1158,6 @@ __global__ __launch_bounds__(256) void k_inter_encode(Geometry g, const FrameSta
 // ------------------------------------------------------------------ intra analysis
 // raster block index -> blkIdx
 __constant__ uint8_t kRasterToBlk[16] = {0, 1, 4, 5, 2, 3, 6, 7, 8, 9, 12, 13, 10, 11, 14, 15};
-__device__ __forceinline__ void wave_sync_lds() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // One wave per macroblock, fully parallel: SATD of the 9 Intra4x4 modes of the 16 blocks
 // (144 block/mode pairs over 64 lanes), of the 4 Intra16x16 modes (one 4x4 block per lane)
@@ -2607,24 +2734,36 @@ void launch_hpel(const Geometry& g, const DeviceBuffers& b, uint8_t* const plane
     sa.publish = publish ? 1 : 0;
     sa.t_start = b.out_hdr ? &b.out_hdr->t_start : nullptr;
     hipLaunchKernelGGL(k_hpel, grid, dim3(256), 0, stream, g, sa, planes[0], planes[1], planes[2], planes[3],
-                       hp_pitch, (const uint8_t*)nullptr);
+                       hp_pitch);
 }
 
-void launch_hpel_of(const Geometry& g, const uint8_t* luma, uint8_t* const planes[4], int hp_pitch, hipStream_t stream) {
-    const int W = g.coded_w + 2 * kHpelPad, H = g.coded_h + 2 * kHpelPad;
-    dim3 grid((W + kHpTW - 1) / kHpTW, (H + kHpTH - 1) / kHpTH);
-    StateArg sa{};  // no state: the picture is given
-    hipLaunchKernelGGL(k_hpel, grid, dim3(256), 0, stream, g, sa, planes[0], planes[1], planes[2], planes[3], hp_pitch,
-                       luma);
+__global__ __launch_bounds__(256) void k_copy_luma(const uint4* __restrict__ src, uint4* __restrict__ dst, size_t n) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;  // 16-byte chunk
+    if (i < n) dst[i] = src[i];
+}
+
+void launch_copy_luma(const Geometry& g, const uint8_t* luma, uint8_t* dst, hipStream_t stream) {
+    const size_t n = (size_t)g.pitch * g.coded_h / 16;  // pitch is a multiple of 256
+    hipLaunchKernelGGL(k_copy_luma, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream,
+                       reinterpret_cast<const uint4*>(luma), reinterpret_cast<uint4*>(dst), n);
+}
+
+void launch_mc_luma_test(const Geometry& g, const uint8_t* ref, int x4, int y4, uint8_t* out, hipStream_t stream) {
+    hipLaunchKernelGGL(k_mc_luma_test, dim3(1), dim3(64), 0, stream, g, ref, x4, y4, out);
 }
 
 void launch_me(const Geometry& g, const DeviceBuffers& b, const uint8_t* src_y, hipStream_t stream,
-               const FrameState* state) {
+               const FrameState* publish, bool side) {
     const int nmb = g.mb_w * g.mb_h;
-    if (state)
-        hipLaunchKernelGGL(k_me_full_val, dim3(nmb), dim3(kMeThreads), 0, stream, g, *state, src_y, b.mb);
+    StateArg sa{};
+    if (publish) sa.v = *publish;
+    sa.dst = b.fs;
+    sa.publish = publish ? 1 : 0;
+    sa.t_start = b.out_hdr ? &b.out_hdr->t_start : nullptr;  // H.264: a P picture's first kernel
+    if (side && publish)
+        hipLaunchKernelGGL(k_me_full_val, dim3(nmb), dim3(kMeThreads), 0, stream, g, sa, src_y, b.mb);
     else
-        hipLaunchKernelGGL(k_me_full, dim3(nmb), dim3(kMeThreads), 0, stream, g, b.fs, src_y, b.mb);
+        hipLaunchKernelGGL(k_me_full, dim3(nmb), dim3(kMeThreads), 0, stream, g, sa, src_y, b.mb);
 }
 
 void launch_inter(const Geometry& g, const DeviceBuffers& b, const uint8_t* src_y, const uint8_t* src_uv,
@@ -2641,7 +2780,7 @@ static void launch_analyze(const Geometry& g, const DeviceBuffers& b, const uint
     if (publish) sa.v = *publish;
     sa.dst = b.fs;
     sa.publish = publish ? 1 : 0;
-    // the first kernel of an I picture stamps the start; in a P picture k_hpel did
+    // the first kernel of an I picture stamps the start; in a P picture k_me_full did
     sa.t_start = (b.out_hdr && first) ? &b.out_hdr->t_start : nullptr;
     hipLaunchKernelGGL(k_intra_analyze, dim3((nmb + 3) / 4), dim3(256), 0, stream, g, sa, src_y, src_uv, b.mb,
                        b.wave_prog, b.intra_gain, b.intra_cand);

@@ -226,11 +226,6 @@ void GpuHevcEncoder::fill_state(FrameSlot& sl, bool idr, int qp, int ref, int cu
     m.me_coarse = cfg_.me_coarse;
     m.subpel = cfg_.subpel;
     m.partitions = 0;  // HEVC codes 16x16 prediction units from the 16x16 vectors
-    m.hp_pitch = hp_pitch_;
-    m.hp_f = hp_[0] + org;
-    m.hp_h = hp_[1] + org;
-    m.hp_v = hp_[2] + org;
-    m.hp_j = hp_[3] + org;
     m.sse_part = sl.buf.sse_part;
 }
 

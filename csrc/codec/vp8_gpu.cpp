@@ -232,11 +232,6 @@ void GpuVp8Encoder::fill_state(Slot& s, bool key, int qp, int ref, int cur) {
     m.search_range = h264::me_range(cfg_.search_range);
     m.me_coarse = cfg_.me_coarse;
     m.subpel = cfg_.subpel ? 1 : 0;  // quarter-sample vectors (VP8 luma precision), six-tap prediction
-    m.hp_pitch = hp_pitch_;
-    m.hp_f = hp_ + org;
-    m.hp_h = (cfg_.subpel ? hp_sub_[0] : hp_) + org;
-    m.hp_v = (cfg_.subpel ? hp_sub_[1] : hp_) + org;
-    m.hp_j = (cfg_.subpel ? hp_sub_[2] : hp_) + org;
 }
 
 void GpuVp8Encoder::enqueue_body(bool key, const uint8_t* src_y, const uint8_t* src_uv) {

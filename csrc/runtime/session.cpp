@@ -130,7 +130,6 @@ Session::Session(const SessionConfig& cfg) : cfg_(cfg) {
         }
         for (int k = 0; k < depth_; ++k)  // GPU-to-GPU only: device-scope release
             HIP_CHECK(hipEventCreateWithFlags(&ev_conv_[k], hipEventDisableTiming | hipEventReleaseToDevice));
-        enc_->set_hpel_side_stream(false);
     }
     if (depth_ > 1 && cfg_.use_graph && !enc_->supports_split())
         throw std::invalid_argument("hipGraph replay with pipeline_depth 2 needs an encoder with the split form");
