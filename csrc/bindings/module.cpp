@@ -145,6 +145,29 @@ PYBIND11_MODULE(_native, m) {
         return h264::luma_qpel(plane.data(), W, W, H, x4, y4);
     });
     h.def("level_for", &h264::pick_level);
+    // the all-zero residual bounds of the P coder and the quantisers they are bounds of
+    h.def("zero_sum_4x4", [](int qp) { return h264::zero_sum_4x4(qp); }, py::arg("qp"));
+    h.def("zero_sum_chroma_dc", [](int qpc) { return h264::zero_sum_chroma_dc(qpc); }, py::arg("qpc"));
+    h.def("chroma_qp", [](int qp, int offset) { return h264::chroma_qp(qp, offset); }, py::arg("qp"),
+          py::arg("offset") = 0);
+    h.def("quant4x4", [](py::array_t<int, py::array::c_style | py::array::forcecast> y, int qp, bool intra, int start) {
+        if (y.size() != 16) throw std::invalid_argument("need 16 values");
+        py::array_t<int> z(16);
+        const int nz = h264::quant4x4(y.data(), z.mutable_data(), qp, intra, start);
+        return py::make_tuple(z, nz);
+    }, py::arg("y"), py::arg("qp"), py::arg("intra") = false, py::arg("start") = 0);
+    h.def("quant_dc_chroma", [](py::array_t<int, py::array::c_style | py::array::forcecast> dc, int qpc, bool intra) {
+        if (dc.size() != 4) throw std::invalid_argument("need 4 values");
+        py::array_t<int> z(4);
+        const int nz = h264::quant_dc_chroma(dc.data(), z.mutable_data(), qpc, intra);
+        return py::make_tuple(z, nz);
+    }, py::arg("dc"), py::arg("qpc"), py::arg("intra") = false);
+    h.def("luma_block_inter", [](py::array_t<int, py::array::c_style | py::array::forcecast> res, int qp) {
+        if (res.size() != 16) throw std::invalid_argument("need 16 values");
+        py::array_t<int> z(16), rr(16);
+        const int nz = h264::luma_block_inter(res.data(), qp, z.mutable_data(), rr.mutable_data());
+        return py::make_tuple(z, rr, nz);
+    }, py::arg("res"), py::arg("qp"), "inter luma block: residual (raster) -> levels (scan), reconstructed residual, nz");
 
     py::class_<h264::EncoderConfig>(m, "EncoderConfig")
         .def(py::init<>())

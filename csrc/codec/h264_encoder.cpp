@@ -335,7 +335,7 @@ GpuH264Encoder::GpuH264Encoder(const EncoderConfig& cfg, hipStream_t stream)
     if (geom_.mb_h > kMaxSlices) throw std::invalid_argument("picture too tall");
     if (geom_.mb_w > 512) throw std::invalid_argument("picture too wide (k_intra_wave stages <= 512 MBs per row)");
     const int nmb = geom_.mb_w * geom_.mb_h;
-    if ((nmb + 3) / 4 + geom_.mb_h > kSsePartStride)
+    if (geom_.mb_h > kSsePartStride)
         throw std::invalid_argument("frame too large for the distortion partials");
     const size_t ysz = (size_t)geom_.pitch * geom_.coded_h, uvsz = ysz / 2;
     for (int i = 0; i < 2; ++i) {
@@ -504,11 +504,16 @@ void GpuH264Encoder::enqueue_analysis_kernels(bool idr, const uint8_t* src_y, co
             launch_me(geom_, sl.buf, src_y, stream_m_, pub, true);
             HIP_CHECK(hipEventRecord(sl.me_done, stream_m_));
             HIP_CHECK(hipStreamWaitEvent(stream_, sl.me_done, 0));
+            launch_inter(geom_, sl.buf, src_y, src_uv, stream_);
+        } else if (!sl.me_unf && geom_.mb_w * geom_.mb_h <= kFusedMaxMbs) {
+            // the search reads the picture the coder predicts from: one kernel searches and codes
+            wait_input();
+            launch_p_fused(geom_, sl.buf, src_y, src_uv, stream_, pub);
         } else {
             wait_input();
             launch_me(geom_, sl.buf, src_y, stream_, pub);
+            launch_inter(geom_, sl.buf, src_y, src_uv, stream_);
         }
-        launch_inter(geom_, sl.buf, src_y, src_uv, stream_);
         if (cfg_.intra_in_p) launch_intra_in_p(geom_, sl.buf, src_y, src_uv, stream_);
     }
 }

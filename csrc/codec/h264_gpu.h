@@ -1,7 +1,8 @@
 // Device data layout and host API of the HIP H.264 encoder.
 //
 // Per-frame kernel chain (all on one HIP stream, graph-capturable):
-//   P frame: k_me_full -> k_inter_encode -> k_intra_analyze -> k_intra_wave
+//   P frame: k_p_fused (or k_me_full -> k_inter_encode when the search runs on the unfiltered
+//            copy of a deblocked reference) -> k_intra_analyze -> k_intra_p (intra_in_p)
 //            -> k_cavlc -> k_scan -> k_pack
 // Both P-frame kernels interpolate the reference's sub-sample positions themselves, from windows of
 // the reconstruction staged in LDS (the HEVC and VP8 encoders still build k_hpel's planes for
@@ -104,11 +105,12 @@ struct FrameState {
     // (profiles/r06_deblock) -- nullptr: ref_y
     const uint8_t* me_ref;
     // distortion partials (Y, U, V, Y outside the mask MBs) over the display area, [4][kSsePartStride]: one per
-    // inter workgroup / intra MB row, reduced by k_scan into OutHeader (no atomics)
+    // MB row (k_intra_wave, k_db_sse, k_intra_p's deltas), reduced by k_scan into OutHeader; the P coder
+    // leaves its sums per macroblock in DeviceBuffers::mb_sse and k_scan_rows adds up its row's
     unsigned long long* sse_part;
 };
 constexpr int kHpelPad = 48;
-constexpr int kSsePartStride = 65536;  // >= ceil(nmb / 4): 8K is 129600 MBs -> 32400 partials
+constexpr int kSsePartStride = 65536;  // >= mb_h (H.264); HEVC: one per 4 CUs or per CTB
 
 // Header written at the start of the device output / host output buffer.
 struct OutHeader {
@@ -162,7 +164,8 @@ struct DeviceBuffers {
     int* wave_prog;         // [1] intra candidate count of P pictures ([0] unused)
     int32_t* intra_gain;    // [nmb] P frames: gain of switching each MB to intra (0 = stays inter)
     int* intra_cand;        // [nmb] P frames: MBs with a positive gain (count in wave_prog[1])
-    uint32_t* mb_sse;       // [3 * nmb] P frames: per-MB inter distortion (replaced for intra MBs)
+    uint32_t* mb_sse;       // [3 * nmb] P frames: per-MB inter distortion (Y, U, V), summed by k_scan_rows; k_intra_p
+                            // adds an intra MB's difference to its row's sse_part
     // in-loop deblocking (h264_deblock.hip)
     uint4* db_rec;          // [nmb] boundary strengths + QP record per MB (k_db_prep)
     int* db_rowq;           // [mb_h] QP of each row's last mb_qp_delta MB (-1: none)
@@ -188,7 +191,17 @@ void launch_copy_luma(const Geometry& g, const uint8_t* luma, uint8_t* dst, hipS
 void launch_mc_luma_test(const Geometry& g, const uint8_t* ref, int x4, int y4, uint8_t* out, hipStream_t stream);
 void launch_inter(const Geometry& g, const DeviceBuffers& b, const uint8_t* src_y, const uint8_t* src_uv,
                   hipStream_t stream);
-// The first kernel of a frame (launch_intra for I, launch_me for P) publishes the frame
+// launch_me + launch_inter as one kernel (k_p_fused): a workgroup per macroblock searches, then codes
+// it on one wave.  For a P picture whose search reads the picture the coder predicts from
+// (FrameState::me_ref null); `publish` as launch_me.  The encoder uses it up to kFusedMaxMbs
+// macroblocks (1080p), where the search leaves compute units idle in its tail and the coding fills
+// them (+1.7 %); at 2560x1440 and 4K the search fills the GPU, and running it at the fused kernel's
+// 6 waves per SIMD instead of k_me_full's 8 costs more than the overlap returns (-4 %, -8 %:
+// profiles/p_fused/NOTES.md).
+constexpr int kFusedMaxMbs = 8160;
+void launch_p_fused(const Geometry& g, const DeviceBuffers& b, const uint8_t* src_y, const uint8_t* src_uv,
+                    hipStream_t stream, const FrameState* publish = nullptr);
+// The first kernel of a frame (launch_intra for I, launch_me / launch_p_fused for P) publishes the frame
 // state: with `publish` non-null it takes the state by value and stores it to b.fs for the
 // later kernels (no copy node); with nullptr it reads b.fs (filled by a memcpy node, hipGraph).
 void launch_intra(const Geometry& g, const DeviceBuffers& b, const uint8_t* src_y, const uint8_t* src_uv,

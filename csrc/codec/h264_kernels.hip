@@ -7,7 +7,11 @@
 //                   quarter-pel refinement; block-wide argmin via shuffles + LDS.
 //  * k_inter_encode one wave per macroblock (4 per workgroup): motion compensation
 //                   (6-tap qpel / bilinear chroma), 4x4 integer transform, quantisation,
-//                   reconstruction into the reference frame.  Fully parallel over MBs.
+//                   reconstruction into the reference frame.  Fully parallel over MBs.  A
+//                   macroblock whose residual is known to quantise to zero runs no transform.
+//  * k_p_fused      k_me_full and k_inter_encode in one kernel: the workgroup that searched a
+//                   macroblock codes it on its wave 0 (P pictures whose search reads the
+//                   picture the coder predicts from; the two kernels remain for the others).
 //  * k_intra_analyze one wave per MB: open-loop Intra4x4 / Intra16x16 / chroma mode costs
 //                   (SATD vs source-neighbour predictions) and the intra / inter decision.
 //  * k_intra_wave   one workgroup per MB row (luma wave + chroma wave): closed-loop coding
@@ -258,6 +262,7 @@ constexpr int kMaxRange = 32;
 constexpr int kWinPadX = 4, kWinPadY = 3;
 constexpr int kWinStride = 16 + 2 * kMaxRange + 8;  // bytes per LDS window row: a full row at R = 32
 constexpr int kWinRows = 16 + 2 * kMaxRange + 7;
+constexpr int kWinWords = kWinRows * kWinStride / 4;
 
 constexpr int kMeThreads = 256, kMeWaves = kMeThreads / 64;
 // F / H / V / J footprints (18x18 each, the layout qpel_lds reads) around `n` (1 or 2) integer
@@ -300,9 +305,14 @@ struct MeState {
 __device__ __forceinline__ MeState me_state(const FrameState& f) {
     return MeState{f.me_ref ? f.me_ref : f.ref_y, f.qp, f.search_range, f.subpel, f.me_coarse, f.partitions};
 }
-__device__ __forceinline__ void me_full_body(const Geometry& g, const MeState& st, const uint8_t* __restrict__ src_y,
-                                             MbInfo* __restrict__ mbs) {
-    __shared__ uint32_t win_lds[kWinRows * kWinStride / 4];
+// Returns the motion it stored in mbs[mbi] (mvx, mvy, part, pmv; the same on every thread): the
+// fused kernel codes the macroblock from it without reading it back.  win_lds: kWinWords of LDS.
+__device__ __forceinline__ MbInfo me_full_body(const Geometry& g, const MeState& st, const uint8_t* __restrict__ src_y,
+                                               MbInfo* __restrict__ mbs, uint32_t* win_lds) {
+    MbInfo out;
+    out.mvx = out.mvy = 0;
+    out.part = kPart16x16;
+    out.pmv[0] = out.pmv[1] = out.pmv[2] = out.pmv[3] = 0;
     __shared__ uint8_t sp2[2][4][18][kSpW];   // sub-sample footprints: the 16x16 match, or two partitions
     __shared__ int16_t fp_b1[2][kFpRows][kSpW];
     __shared__ uint32_t srcw[64];
@@ -342,7 +352,7 @@ __device__ __forceinline__ void me_full_body(const Geometry& g, const MeState& s
                 m.part = kPart16x16;
                 m.pmv[0] = m.pmv[1] = m.pmv[2] = m.pmv[3] = 0;
             }
-            return;  // uniform across the workgroup
+            return out;  // uniform across the workgroup
         }
     }
     // search window straight from the reference picture, edge-clamped.  Its left edge x0 - R - 4 is
@@ -668,7 +678,14 @@ __device__ __forceinline__ void me_full_body(const Geometry& g, const MeState& s
                 m.pmv[2] = (int16_t)pvx[1];
                 m.pmv[3] = (int16_t)pvy[1];
             }
-            return;  // uniform
+            out.mvx = (int16_t)mvx;
+            out.mvy = (int16_t)mvy;
+            out.part = (uint8_t)part;
+            out.pmv[0] = (int16_t)pvx[0];
+            out.pmv[1] = (int16_t)pvy[0];
+            out.pmv[2] = (int16_t)pvx[1];
+            out.pmv[3] = (int16_t)pvy[1];
+            return out;  // uniform
         }
     }
 
@@ -724,6 +741,9 @@ __device__ __forceinline__ void me_full_body(const Geometry& g, const MeState& s
         m.part = kPart16x16;
         m.pmv[0] = m.pmv[1] = m.pmv[2] = m.pmv[3] = 0;
     }
+    out.mvx = (int16_t)mvx;
+    out.mvy = (int16_t)mvy;
+    return out;
 }
 
 // The search is the first kernel of an H.264 P picture: it publishes the frame state for the later
@@ -732,13 +752,15 @@ __device__ __forceinline__ void me_full_body(const Geometry& g, const MeState& s
 // the same body, always with the state by value (a name of its own in kernel traces).
 __global__ __launch_bounds__(kMeThreads) void k_me_full(Geometry g, StateArg sa, const uint8_t* __restrict__ src_y,
                                                         MbInfo* __restrict__ mbs) {
+    __shared__ uint32_t win_lds[kWinWords];
     publish_state(sa);
-    me_full_body(g, sa.publish ? me_state(sa.v) : me_state(*sa.dst), src_y, mbs);
+    me_full_body(g, sa.publish ? me_state(sa.v) : me_state(*sa.dst), src_y, mbs, win_lds);
 }
 __global__ __launch_bounds__(kMeThreads) void k_me_full_val(Geometry g, StateArg sa, const uint8_t* __restrict__ src_y,
                                                             MbInfo* __restrict__ mbs) {
+    __shared__ uint32_t win_lds[kWinWords];
     publish_state(sa);
-    me_full_body(g, me_state(sa.v), src_y, mbs);
+    me_full_body(g, me_state(sa.v), src_y, mbs, win_lds);
 }
 
 // ------------------------------------------------------------------ inter encode
@@ -915,42 +937,63 @@ __global__ __launch_bounds__(64) void k_mc_luma_test(Geometry g, const uint8_t* 
     reinterpret_cast<uint32_t*>(out)[lane] = p;  // lane = 4 * row + dword of the row
 }
 
-__global__ __launch_bounds__(256) void k_inter_encode(Geometry g, const FrameState* __restrict__ fs,
-                                                       const uint8_t* __restrict__ src_y,
-                                                       const uint8_t* __restrict__ src_uv, MbInfo* __restrict__ mbs,
-                                                       int16_t* __restrict__ coef, uint32_t* __restrict__ mb_sse,
-                                                       int* __restrict__ wave_prog) {
-    __shared__ uint8_t pred[4][384];
-    __shared__ int16_t res[4][384];
-    __shared__ uint32_t mcw[4][2 * kMcWords];  // per wave: the windows of fractional vectors' prediction
-    __shared__ int cdc[4][8];
-    __shared__ int cdc_nz[4][2];
-
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+// What the coder reads of the frame state, taken once into scalar registers (as MeState).
+struct CodeState {
+    const uint8_t* ref_y;
+    const uint8_t* ref_uv;
+    uint8_t* rec_y;
+    uint8_t* rec_uv;
+    const uint8_t* prev_src;
+    uint8_t* save_src;
+    int qp, aq, intra_in_p, chroma_qp_offset;
+};
+__device__ __forceinline__ CodeState code_state(const FrameState& f) {
+    return CodeState{f.ref_y, f.ref_uv, f.rec_y, f.rec_uv, f.prev_src, f.save_src, f.qp, f.aq, f.intra_in_p,
+                     f.chroma_qp_offset};
+}
+// LDS of one coding wave
+struct InterLds {
+    __attribute__((aligned(4))) uint8_t pred[384];
+    int16_t res[384];
+    uint32_t mcw[2 * kMcWords];  // the windows of fractional vectors' prediction
+    int cdc[8];
+    int cdc_nz[2];
+};
+// One P macroblock coded by one wave (whole wave active): prediction under the motion `mi`
+// (mvx / mvy / part / pmv), residual, transforms or their shortcuts, reconstruction, the rest of
+// MbInfo and the macroblock's distortion (mb_sse[c * nmb + mbi], c = Y, U, V: k_scan_rows sums
+// them).  L is the wave's own; it synchronises with wave_sync_lds() only.
+__device__ __forceinline__ void inter_code_mb(const Geometry& g, const CodeState& fs, const uint8_t* __restrict__ src_y,
+                                              const uint8_t* __restrict__ src_uv, MbInfo* __restrict__ mbs,
+                                              int16_t* __restrict__ coef, uint32_t* __restrict__ mb_sse, int mbi,
+                                              int lane, const MbInfo& motion, InterLds& L) {
+    // the motion is the same on every lane: kept in scalar registers
+    MbInfo mi;
+    mi.mvx = (int16_t)__builtin_amdgcn_readfirstlane((int)motion.mvx);
+    mi.mvy = (int16_t)__builtin_amdgcn_readfirstlane((int)motion.mvy);
+    mi.part = (uint8_t)__builtin_amdgcn_readfirstlane((int)motion.part);
+    for (int i = 0; i < 4; ++i) mi.pmv[i] = (int16_t)__builtin_amdgcn_readfirstlane((int)motion.pmv[i]);
     const int nmb = g.mb_w * g.mb_h;
-    const int bid = blockIdx.x;
-    const int mbi = bid * 4 + wave;
-    if (bid == 0 && threadIdx.x == 0) wave_prog[1] = 0;  // k_intra_analyze's candidate list (next kernel)
-    const bool valid = mbi < nmb;
-    const int mbx = valid ? mbi % g.mb_w : 0, mby = valid ? mbi / g.mb_w : 0;
+    const int mbx = mbi % g.mb_w, mby = mbi / g.mb_w;
     const int x0 = mbx * 16, y0 = mby * 16;
-    const uint8_t* __restrict__ ref_y = fs->ref_y;
+    const uint8_t* __restrict__ ref_y = fs.ref_y;
     const bool ref_dwords = (g.pitch & 3) == 0 && (reinterpret_cast<uintptr_t>(ref_y) & 3) == 0;
-    const uint8_t* ref_uv = fs->ref_uv;
+    const uint8_t* ref_uv = fs.ref_uv;
     const int cw = g.coded_w / 2, ch = g.coded_h / 2;
     int mvx = 0, mvy = 0;
     int lsad = 0;  // this lane's share of sum |luma residual| (adaptive quantisation)
     int tsad = 0;  // this lane's share of sum |src - previous src| (temporal class, aq 3)
-    MbInfo mi;      // this MB's motion (16x16 or two partitions: each lane's samples use their own vector)
-    mi.part = kPart16x16;
-    if (valid) {
-        mi = mbs[mbi];
+    // "load" layout: lane 4 * r + q holds samples 4q .. 4q+3 of luma row r (source sw, prediction pw)
+    // and chroma sample (lane & 7, lane >> 3) of both planes (prediction cpv, residual crs)
+    uint32_t sw = 0, pw = 0;
+    int cpv[2] = {0, 0}, crs[2] = {0, 0};
+    {
         const int r = lane >> 2, c0 = (lane & 3) * 4;
         const Mv lv = px_mv(mi, c0, r);  // the lane's 4 luma samples lie in one partition
         mvx = lv.x;
         mvy = lv.y;
-        const uint32_t sw = *reinterpret_cast<const uint32_t*>(src_y + (y0 + r) * g.pitch + x0 + c0);
-        if (fs->aq >= 3) {
+        sw = *reinterpret_cast<const uint32_t*>(src_y + (y0 + r) * g.pitch + x0 + c0);
+        if (fs.aq >= 3) {
             // temporal class (h264_mb.h temporal_class): the source against the previous source,
             // displaced by the vector's integer part; this MB's source becomes the next frame's
             const int ix = mvx >> 2, iy = mvy >> 2;
@@ -959,16 +1002,16 @@ __global__ __launch_bounds__(256) void k_inter_encode(Geometry g, const FrameSta
             // unaligned and the second stays inside the row's pitch
             if (px >= 0 && px + 4 <= g.coded_w && py >= 0 && py < g.coded_h &&
                 ((px & 3) == 0 || (px & ~3) + 8 <= g.pitch)) {
-                const uint32_t* qa = reinterpret_cast<const uint32_t*>(fs->prev_src + (size_t)py * g.pitch + (px & ~3));
+                const uint32_t* qa = reinterpret_cast<const uint32_t*>(fs.prev_src + (size_t)py * g.pitch + (px & ~3));
                 const uint32_t sh = (uint32_t)(px & 3);
-                const uint32_t pw = sh ? __builtin_amdgcn_alignbyte(qa[1], qa[0], sh) : qa[0];
-                tsad = (int)__builtin_amdgcn_sad_u8(sw, pw, 0u);
+                const uint32_t qw = sh ? __builtin_amdgcn_alignbyte(qa[1], qa[0], sh) : qa[0];
+                tsad = (int)__builtin_amdgcn_sad_u8(sw, qw, 0u);
             } else {
                 for (int k = 0; k < 4; ++k)
                     tsad += abs((int)((sw >> (8 * k)) & 0xff) -
-                                ref_px(fs->prev_src, g.pitch, g.coded_w, g.coded_h, x0 + c0 + k + ix, y0 + r + iy));
+                                ref_px(fs.prev_src, g.pitch, g.coded_w, g.coded_h, x0 + c0 + k + ix, y0 + r + iy));
             }
-            *reinterpret_cast<uint32_t*>(fs->save_src + (y0 + r) * g.pitch + x0 + c0) = sw;
+            *reinterpret_cast<uint32_t*>(fs.save_src + (y0 + r) * g.pitch + x0 + c0) = sw;
         }
         // luma prediction from the reference picture; the macroblock's one or two vectors are
         // uniform across the wave (the lane's 4 samples lie in partition lpi: vector (mvx, mvy))
@@ -976,11 +1019,10 @@ __global__ __launch_bounds__(256) void k_inter_encode(Geometry g, const FrameSta
         const Mv va = blk_mv(mi, 0, 0), vb = blk_mv(mi, part == kPart8x16 ? 2 : 0, part == kPart16x8 ? 2 : 0);
         const int vax = __builtin_amdgcn_readfirstlane(va.x), vay = __builtin_amdgcn_readfirstlane(va.y);
         const int vbx = __builtin_amdgcn_readfirstlane(vb.x), vby = __builtin_amdgcn_readfirstlane(vb.y);
-        uint32_t pw = 0;  // the lane's 4 predicted samples
         if ((vax | vay | vbx | vby) & 3) {
             // a fractional vector: interpolated from the block's window(s) staged in LDS
             const int lpi = part == kPart16x8 ? (r >> 3) : (part == kPart8x16 ? (c0 >> 3) : 0);
-            mc_luma_wave(mcw[wave], ref_y, g.pitch, g.coded_w, g.coded_h, part == kPart16x16 ? 1 : 2, x0 * 4 + vax,
+            mc_luma_wave(L.mcw, ref_y, g.pitch, g.coded_w, g.coded_h, part == kPart16x16 ? 1 : 2, x0 * 4 + vax,
                          y0 * 4 + vay, x0 * 4 + vbx, y0 * 4 + vby, lane, lpi, &pw);
         } else {
             // full-sample vectors (static desktop, scrolled text): 4 bytes of the reference row (edge
@@ -995,155 +1037,222 @@ __global__ __launch_bounds__(256) void k_inter_encode(Geometry g, const FrameSta
                     pw |= (uint32_t)ref_px(ref_y, g.pitch, g.coded_w, g.coded_h, px + k, py) << (8 * k);
             }
         }
-        for (int k = 0; k < 4; ++k) {
-            const int p = (int)((pw >> (8 * k)) & 0xff);
-            const int d = (int)((sw >> (8 * k)) & 0xff) - p;
-            pred[wave][r * 16 + c0 + k] = (uint8_t)p;
-            res[wave][r * 16 + c0 + k] = (int16_t)d;
-            lsad += d < 0 ? -d : d;
-        }
+        lsad = (int)__builtin_amdgcn_sad_u8(sw, pw, 0u);
         const int cr_ = lane >> 3, cc = lane & 7;
         const int xc = x0 / 2 + cc, yc = y0 / 2 + cr_;
         const Mv cv = px_mv(mi, 2 * cc, 2 * cr_);
         for (int comp = 0; comp < 2; ++comp) {
-            const int p = chroma_pred8(ref_uv, g.pitch, cw, ch, comp, xc * 8 + cv.x, yc * 8 + cv.y);
-            const int sv = src_uv[yc * g.pitch + 2 * xc + comp];
-            pred[wave][256 + comp * 64 + cr_ * 8 + cc] = (uint8_t)p;
-            res[wave][256 + comp * 64 + cr_ * 8 + cc] = (int16_t)(sv - p);
+            cpv[comp] = chroma_pred8(ref_uv, g.pitch, cw, ch, comp, xc * 8 + cv.x, yc * 8 + cv.y);
+            crs[comp] = (int)src_uv[yc * g.pitch + 2 * xc + comp] - cpv[comp];
         }
     }
-    __syncthreads();
+    const int aq = fs.aq;
+    const bool want_cost = fs.intra_in_p != 0;  // MbInfo::cost (the SATD) is read by k_intra_analyze alone
     const uint32_t lsad_mb = (uint32_t)wave_sum(lsad);
     const int tcls = temporal_class((uint32_t)wave_sum(tsad), __ballot((mvx | mvy) != 0) == 0ull);
-    const int qp = mb_qp_for(fs->qp, lsad_mb, tcls, fs->aq);  // wave-uniform
-    const int qpc = chroma_qp(qp, fs->chroma_qp_offset);
-    int16_t* mc = coef + (size_t)(valid ? mbi : 0) * kCoefStride;
+    const int qp = mb_qp_for(fs.qp, lsad_mb, tcls, aq);  // wave-uniform
+    const int qpc = chroma_qp(qp, fs.chroma_qp_offset);
+    int16_t* mc = coef + (size_t)mbi * kCoefStride;
+
+    // ---- residuals known to quantise to zero (h264_mb.h zero_sum_4x4 / zero_sum_chroma_dc): the
+    // macroblock's luma, or its chroma, then takes a shortcut that runs no transform -- levels 0,
+    // reconstruction = prediction, distortion = sum residual^2 -- which is what the transforms give.
+    // Both tests are wave-uniform.  Luma: a 4x4 block is lanes q, q + 4, q + 8, q + 12 of a row of 16.
+    int bsum = lsad;
+    bsum += __builtin_amdgcn_mov_dpp(bsum, 0x124, 0xF, 0xF, false);  // row_ror:4
+    bsum += __builtin_amdgcn_mov_dpp(bsum, 0x128, 0xF, 0xF, false);  // row_ror:8
+    const bool luma_zero = __ballot(bsum > zero_sum_4x4(qp)) == 0ull;
+    // Chroma, U in the low and V in the high half-word (a plane sums to <= 64 * 255): block =
+    // lanes that differ in bits 0, 1 (column) and 3, 4 (row); plane = also bits 2 and 5.
+    int csum = abs(crs[0]) | (abs(crs[1]) << 16);
+    csum += __builtin_amdgcn_mov_dpp(csum, 0xB1, 0xF, 0xF, false);   // quad_perm [1,0,3,2]
+    csum += __builtin_amdgcn_mov_dpp(csum, 0x4E, 0xF, 0xF, false);   // quad_perm [2,3,0,1]
+    csum += __builtin_amdgcn_mov_dpp(csum, 0x128, 0xF, 0xF, false);  // row_ror:8 = lane ^ 8
+    {
+        const auto r16 = __builtin_amdgcn_permlane16_swap((uint32_t)csum, (uint32_t)csum, false, false);
+        csum = (int)(r16[0] + r16[1]);  // lane ^ 16
+    }
+    int psum = csum + __builtin_amdgcn_mov_dpp(csum, 0x124, 0xF, 0xF, false);  // row_ror:4: bit 2 flipped
+    {
+        const auto r32 = __builtin_amdgcn_permlane32_swap((uint32_t)psum, (uint32_t)psum, false, false);
+        psum = (int)(r32[0] + r32[1]);  // lane ^ 32
+    }
+    const int zac = zero_sum_4x4(qpc), zdc = zero_sum_chroma_dc(qpc);
+    const bool chroma_bound = __ballot((csum & 0xffff) > zac || (csum >> 16) > zac || (psum & 0xffff) > zdc ||
+                                       (psum >> 16) > zdc) == 0ull;
+    // the transforms' "row" layout goes through LDS; the shortcuts work on the load layout
+    const bool luma_rows = !luma_zero || want_cost;
+    if (luma_rows) {
+        const int r = lane >> 2, c0 = (lane & 3) * 4;
+        *reinterpret_cast<uint32_t*>(&L.pred[r * 16 + c0]) = pw;
+        for (int k = 0; k < 4; ++k) L.res[r * 16 + c0 + k] = (int16_t)(byte_of(sw, k) - byte_of(pw, k));
+    }
+    if (!chroma_bound) {
+        for (int comp = 0; comp < 2; ++comp) {
+            L.pred[256 + comp * 64 + lane] = (uint8_t)cpv[comp];  // lane = 8 * row + column
+            L.res[256 + comp * 64 + lane] = (int16_t)crs[comp];
+        }
+    }
+    wave_sync_lds();
 
     // ---- luma: lane = 4 * blkIdx + row
     const int lb = lane >> 2, rr = lane & 3, lbx = kBlkX[lb], lby = kBlkY[lb];
-    int x[4], y[4], z[4], rres[4];
+    int x[4] = {0, 0, 0, 0};
     const int ro = (lby * 4 + rr) * 16 + lbx * 4;  // row offset in the MB's pred / res
+    uint32_t satd_mb = 0;
+    if (luma_rows) {
 #pragma unroll
-    for (int c = 0; c < 4; ++c) x[c] = res[wave][ro + c];
-    const int hs = quad_sum(had_row_abs(x, rr));
-    fdct_row(x, rr, y);
-    const int nzb = quad_sum(quant_row(y, rr, qp, false, 0, z));
-    {
-        int d[4];
-        dequant_row(z, rr, qp, d);
-        idct_row(d, rr, rres);
-    }
-    int d_pred = 0, d_coded = 0;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        const int pv = pred[wave][ro + c];
-        const int e = pv + x[c] - clip255(pv + rres[c]);
-        d_pred += x[c] * x[c];
-        d_coded += e * e;
-    }
-    const uint32_t bits = rr == 0 ? block_bits_est(nzb) : 0u;
-    const bool drop = valid && drop_luma_for(fs->aq, lsad_mb, tcls, qp, wave_sum(d_pred), wave_sum(d_coded),
-                                             (uint32_t)wave_sum((int)bits));  // wave-uniform
-    const bool drop_c = drop_chroma_for(fs->aq, tcls, drop);
-    const int nz_l = drop ? 0 : nzb;
-    int sse_y = 0;
-    if (valid) {
-        uint32_t packed = 0;
-        const bool vis = x0 + lbx * 4 < g.width && (y0 + lby * 4 + rr) < g.height;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            if (drop) z[c] = rres[c] = 0;
-            mc[kCoefLuma + lb * 16 + kZigzagInv4x4[rr * 4 + c]] = (int16_t)z[c];
-            const int pv = pred[wave][ro + c];
-            const int v = clip255(pv + rres[c]);
-            const int e = pv + x[c] - v;
-            sse_y += vis ? e * e : 0;
-            packed |= (uint32_t)v << (8 * c);
+        for (int c = 0; c < 4; ++c) x[c] = L.res[ro + c];
+        if (want_cost) {
+            const int hs = quad_sum(had_row_abs(x, rr));
+            satd_mb = (uint32_t)wave_sum(rr == 0 ? (hs + 1) >> 1 : 0);
         }
-        *reinterpret_cast<uint32_t*>(fs->rec_y + (y0 + lby * 4 + rr) * g.pitch + x0 + lbx * 4) = packed;
-        if (rr == 0) mbs[mbi].nz_luma[lby * 4 + lbx] = (uint8_t)nz_l;
     }
-    const uint32_t satd_mb = (uint32_t)wave_sum(rr == 0 ? (hs + 1) >> 1 : 0);
+    bool drop = false;
+    int nz_l = 0, sse_y = 0;
+    if (luma_zero) {
+        // No level of any block: cbp gets no luma bit, so no reader (k_cavlc's code_role) looks at
+        // this macroblock's luma coefficients and none are stored.  drop_luma_for is false with a
+        // bit estimate of 0.
+        {
+            const int r = lane >> 2, c0 = (lane & 3) * 4;
+            const bool vis = x0 + c0 < g.width && (y0 + r) < g.height;
+            for (int k = 0; k < 4; ++k) {
+                const int e = byte_of(sw, k) - byte_of(pw, k);
+                sse_y += vis ? e * e : 0;
+            }
+            *reinterpret_cast<uint32_t*>(fs.rec_y + (y0 + r) * g.pitch + x0 + c0) = pw;
+            if (lane < 4) reinterpret_cast<uint32_t*>(mbs[mbi].nz_luma)[lane] = 0u;
+        }
+    } else {
+        int y[4], z[4], rres[4];
+        fdct_row(x, rr, y);
+        const int nzb = quad_sum(quant_row(y, rr, qp, false, 0, z));
+        {
+            int d[4];
+            dequant_row(z, rr, qp, d);
+            idct_row(d, rr, rres);
+        }
+        if (drop_luma_possible(aq, lsad_mb, tcls)) {  // wave-uniform
+            int d_pred = 0, d_coded = 0;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                const int pv = L.pred[ro + c];
+                const int e = pv + x[c] - clip255(pv + rres[c]);
+                d_pred += x[c] * x[c];
+                d_coded += e * e;
+            }
+            const uint32_t bits = rr == 0 ? block_bits_est(nzb) : 0u;
+            drop = drop_luma_for(aq, lsad_mb, tcls, qp, wave_sum(d_pred), wave_sum(d_coded),
+                                          (uint32_t)wave_sum((int)bits));
+        }
+        nz_l = drop ? 0 : nzb;
+        {
+            uint32_t packed = 0;
+            const bool vis = x0 + lbx * 4 < g.width && (y0 + lby * 4 + rr) < g.height;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                if (drop) z[c] = rres[c] = 0;
+                mc[kCoefLuma + lb * 16 + kZigzagInv4x4[rr * 4 + c]] = (int16_t)z[c];
+                const int pv = L.pred[ro + c];
+                const int v = clip255(pv + rres[c]);
+                const int e = pv + x[c] - v;
+                sse_y += vis ? e * e : 0;
+                packed |= (uint32_t)v << (8 * c);
+            }
+            *reinterpret_cast<uint32_t*>(fs.rec_y + (y0 + lby * 4 + rr) * g.pitch + x0 + lbx * 4) = packed;
+            if (rr == 0) mbs[mbi].nz_luma[lby * 4 + lbx] = (uint8_t)nz_l;
+        }
+    }
+    const bool drop_c = drop_chroma_for(aq, tcls, drop);
 
     // ---- chroma: lanes 0..31, lane = 4 * (comp * 4 + blk) + row
     const int cbk = lane >> 2, ccomp = (cbk >> 2) & 1, cblk = cbk & 3, cbx = cblk & 1, cby = cblk >> 1;
     const int co = 256 + ccomp * 64 + (cby * 4 + rr) * 8 + cbx * 4;
     const bool clane = lane < 32;
-    int cz[4], nzc = 0;
-    if (clane) {
-        int cx[4], cy[4];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) cx[c] = drop_c ? 0 : res[wave][co + c];  // a dropped MB codes no chroma residual
-        fdct_row(cx, rr, cy);
-        if (rr == 0) cdc[wave][ccomp * 4 + cblk] = cy[0];
-        nzc = quant_row(cy, rr, qpc, false, 1, cz);
-    }
-    nzc = quad_sum(nzc);
-    if (valid && clane) {
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            const int i = rr * 4 + c;
-            if (i > 0) mc[kCoefChromaAc + (ccomp * 4 + cblk) * 16 + kZigzagInv4x4[i]] = (int16_t)cz[c];
+    int nzc = 0, dc_any = 0;
+    int sse_u = 0, sse_v = 0;  // this lane's share of the planes' distortion
+    if (chroma_bound || drop_c) {
+        // Every AC and DC level is 0 (a dropped macroblock codes no chroma residual either): cbp
+        // gets chroma 0, so no reader looks at the chroma coefficients and none are stored.
+        {
+            const int xc = x0 / 2 + (lane & 7), yc = y0 / 2 + (lane >> 3);
+            const bool vis = 2 * xc < g.width && 2 * yc < g.height;
+            sse_u = vis ? crs[0] * crs[0] : 0;
+            sse_v = vis ? crs[1] * crs[1] : 0;
+            uint8_t* o = fs.rec_uv + yc * g.pitch + 2 * xc;
+            if (((reinterpret_cast<uintptr_t>(fs.rec_uv) | (uintptr_t)g.pitch) & 1) == 0) {
+                *reinterpret_cast<uint16_t*>(o) = (uint16_t)(cpv[0] | (cpv[1] << 8));
+            } else {
+                o[0] = (uint8_t)cpv[0];
+                o[1] = (uint8_t)cpv[1];
+            }
+            if (lane < 2) reinterpret_cast<uint32_t*>(mbs[mbi].nz_cb)[lane] = 0u;  // nz_cb, nz_cr
         }
-        if (rr == 0) (ccomp ? mbs[mbi].nz_cr : mbs[mbi].nz_cb)[cblk] = (uint8_t)nzc;
-    }
-    __syncthreads();
-    if (valid && (lane == 0 || lane == 16)) {
-        const int comp = lane >> 4;
-        int in[4], zd[4], dq[4];
-        for (int i = 0; i < 4; ++i) in[i] = cdc[wave][comp * 4 + i];
-        const int n = quant_dc_chroma(in, zd, qpc, false);
-        for (int i = 0; i < 4; ++i) mc[kCoefChromaDc + comp * 4 + i] = (int16_t)zd[i];
-        dequant_dc_chroma(zd, dq, qpc);
-        for (int i = 0; i < 4; ++i) cdc[wave][comp * 4 + i] = dq[i];
-        cdc_nz[wave][comp] = n;
-    }
-    __syncthreads();
-    int sse_c = 0;
-    if (clane) {
-        int d[4], cr[4];
-        dequant_row(cz, rr, qpc, d);
-        if (rr == 0) d[0] = cdc[wave][ccomp * 4 + cblk];
-        idct_row(d, rr, cr);
-        if (valid) {
-            const int xc = x0 / 2 + cbx * 4, yc = y0 / 2 + cby * 4 + rr;
+    } else {
+        int cz[4];
+        if (clane) {
+            int cx[4], cy[4];
+#pragma unroll
+            for (int c = 0; c < 4; ++c) cx[c] = L.res[co + c];
+            fdct_row(cx, rr, cy);
+            if (rr == 0) L.cdc[ccomp * 4 + cblk] = cy[0];
+            nzc = quant_row(cy, rr, qpc, false, 1, cz);
+        }
+        nzc = quad_sum(nzc);
+        if (clane) {
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
-                const int v = clip255(pred[wave][co + c] + cr[c]);
-                const int e = pred[wave][co + c] + res[wave][co + c] - v;
-                sse_c += (2 * (xc + c) < g.width && 2 * yc < g.height) ? e * e : 0;
-                fs->rec_uv[yc * g.pitch + 2 * (xc + c) + ccomp] = (uint8_t)v;
+                const int i = rr * 4 + c;
+                if (i > 0) mc[kCoefChromaAc + (ccomp * 4 + cblk) * 16 + kZigzagInv4x4[i]] = (int16_t)cz[c];
+            }
+            if (rr == 0) (ccomp ? mbs[mbi].nz_cr : mbs[mbi].nz_cb)[cblk] = (uint8_t)nzc;
+        }
+        wave_sync_lds();
+        if ((lane == 0 || lane == 16)) {
+            const int comp = lane >> 4;
+            int in[4], zd[4], dq[4];
+            for (int i = 0; i < 4; ++i) in[i] = L.cdc[comp * 4 + i];
+            const int n = quant_dc_chroma(in, zd, qpc, false);
+            for (int i = 0; i < 4; ++i) mc[kCoefChromaDc + comp * 4 + i] = (int16_t)zd[i];
+            dequant_dc_chroma(zd, dq, qpc);
+            for (int i = 0; i < 4; ++i) L.cdc[comp * 4 + i] = dq[i];
+            L.cdc_nz[comp] = n;
+        }
+        wave_sync_lds();
+        if (clane) {
+            int d[4], cr[4];
+            dequant_row(cz, rr, qpc, d);
+            if (rr == 0) d[0] = L.cdc[ccomp * 4 + cblk];
+            idct_row(d, rr, cr);
+            {
+                const int xc = x0 / 2 + cbx * 4, yc = y0 / 2 + cby * 4 + rr;
+                int sse_c = 0;
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    const int v = clip255(L.pred[co + c] + cr[c]);
+                    const int e = L.pred[co + c] + L.res[co + c] - v;
+                    sse_c += (2 * (xc + c) < g.width && 2 * yc < g.height) ? e * e : 0;
+                    fs.rec_uv[yc * g.pitch + 2 * (xc + c) + ccomp] = (uint8_t)v;
+                }
+                (ccomp ? sse_v : sse_u) = sse_c;  // U on lanes 0..15, V on 16..31
             }
         }
+        dc_any = L.cdc_nz[0] | L.cdc_nz[1];
     }
     {
-        // Y on all lanes, U on lanes 0..15, V on 16..31
         const int sy = wave_sum(sse_y);
-        const int su = wave_sum(lane < 16 ? sse_c : 0);
-        const int sv = wave_sum((lane >= 16 && lane < 32) ? sse_c : 0);
-        if (valid && fs->intra_in_p && lane < 3)  // per-MB copy: replaced if the MB switches to intra
-            mb_sse[lane * nmb + mbi] = (uint32_t)(lane == 0 ? sy : (lane == 1 ? su : sv));
-        __shared__ uint32_t part[4][4];
-        if (lane == 0) {
-            part[0][wave] = valid ? (uint32_t)sy : 0u;
-            part[1][wave] = valid ? (uint32_t)su : 0u;
-            part[2][wave] = valid ? (uint32_t)sv : 0u;
-            part[3][wave] = (valid && mb_unmasked(fs, mbx, mby)) ? (uint32_t)sy : 0u;
-        }
-        __syncthreads();
-        if (threadIdx.x < 4) {
-            const int c = threadIdx.x;
-            fs->sse_part[c * kSsePartStride + bid] =
-                (unsigned long long)part[c][0] + part[c][1] + part[c][2] + part[c][3];
-        }
+        const int su = wave_sum(sse_u);
+        const int sv = wave_sum(sse_v);
+        if (lane < 3) mb_sse[lane * nmb + mbi] = (uint32_t)(lane == 0 ? sy : (lane == 1 ? su : sv));
     }
-    const unsigned long long luma_mask = __ballot(valid && rr == 0 && nz_l > 0);    // bit 4b: block b
-    const unsigned long long chroma_mask = __ballot(valid && clane && rr == 0 && nzc > 0);
-    if (valid && lane == 0) {
+    const unsigned long long luma_mask = __ballot(rr == 0 && nz_l > 0);    // bit 4b: block b
+    const unsigned long long chroma_mask = __ballot(clane && rr == 0 && nzc > 0);
+    if (lane == 0) {
         int cbp = 0;
         for (int b8 = 0; b8 < 4; ++b8)
             if ((luma_mask >> (16 * b8)) & 0x1111ull) cbp |= 1 << b8;
-        const int cc = (chroma_mask != 0) ? 2 : ((cdc_nz[wave][0] | cdc_nz[wave][1]) ? 1 : 0);
+        const int cc = (chroma_mask != 0) ? 2 : (dc_any ? 1 : 0);
         cbp |= cc << 4;
         MbInfo& m = mbs[mbi];
         m.type = kMbP16x16;
@@ -1151,8 +1260,46 @@ __global__ __launch_bounds__(256) void k_inter_encode(Geometry g, const FrameSta
         m.qp = (uint8_t)qp;
         m.i16_mode = 0;
         m.chroma_mode = 0;
-        m.cost = inter_cost_mb(satd_mb, fs->qp, mi);
+        m.cost = want_cost ? inter_cost_mb(satd_mb, fs.qp, mi) : 0u;
     }
+}
+
+// The coder as a kernel of its own (a picture whose search ran beside the reference's in-loop
+// filter): four macroblocks per workgroup, a wave each, independent of one another.
+__global__ __launch_bounds__(256) void k_inter_encode(Geometry g, const FrameState* __restrict__ fs,
+                                                       const uint8_t* __restrict__ src_y,
+                                                       const uint8_t* __restrict__ src_uv, MbInfo* __restrict__ mbs,
+                                                       int16_t* __restrict__ coef, uint32_t* __restrict__ mb_sse,
+                                                       int* __restrict__ wave_prog) {
+    __shared__ InterLds lds[4];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int mbi = blockIdx.x * 4 + wave;
+    if (blockIdx.x == 0 && threadIdx.x == 0) wave_prog[1] = 0;  // k_intra_analyze's candidate list (next kernel)
+    if (mbi >= g.mb_w * g.mb_h) return;  // the whole wave
+    const MbInfo mi = mbs[mbi];
+    inter_code_mb(g, code_state(*fs), src_y, src_uv, mbs, coef, mb_sse, mbi, lane, mi, lds[wave]);
+}
+
+// One kernel per P picture whose search reads the picture the coder predicts from: a workgroup per
+// macroblock searches as k_me_full does, then its wave 0 codes the macroblock with the vectors just
+// decided while the other waves leave.  The coder's LDS lies over the search window, which nobody
+// reads any more by then.  The first kernel of the picture: publishes the frame state (StateArg).
+// (6 waves per SIMD asked for: left alone the allocation ends one register over that step)
+__global__ __launch_bounds__(kMeThreads) __attribute__((amdgpu_waves_per_eu(6))) void k_p_fused(Geometry g, StateArg sa, const uint8_t* __restrict__ src_y,
+                                                        const uint8_t* __restrict__ src_uv, MbInfo* __restrict__ mbs,
+                                                        int16_t* __restrict__ coef, uint32_t* __restrict__ mb_sse,
+                                                        int* __restrict__ wave_prog) {
+    __shared__ uint32_t win_lds[kWinWords];
+    static_assert(sizeof(InterLds) <= sizeof(uint32_t) * kWinWords, "the coder's LDS aliases the search window");
+    publish_state(sa);
+    if (blockIdx.x == 0 && threadIdx.x == 0) wave_prog[1] = 0;  // k_intra_analyze's candidate list (next kernel)
+    const MeState st = sa.publish ? me_state(sa.v) : me_state(*sa.dst);
+    const CodeState cs = sa.publish ? code_state(sa.v) : code_state(*sa.dst);
+    const MbInfo mi = me_full_body(g, st, src_y, mbs, win_lds);  // the same on every thread
+    __syncthreads();  // every wave is done with the window
+    if (threadIdx.x >= 64) return;
+    inter_code_mb(g, cs, src_y, src_uv, mbs, coef, mb_sse, blockIdx.x, threadIdx.x, mi,
+                  *reinterpret_cast<InterLds*>(win_lds));
 }
 
 // ------------------------------------------------------------------ intra analysis
@@ -1181,7 +1328,7 @@ __global__ __launch_bounds__(256) void k_intra_analyze(Geometry g, StateArg sa, 
     if (blockIdx.x == 0) {
         if (!fs->idr)  // k_intra_p's per-row distortion deltas (atomically accumulated)
             for (int i = threadIdx.x; i < 4 * g.mb_h; i += 256)
-                fs->sse_part[(i / g.mb_h) * kSsePartStride + (g.mb_w * g.mb_h + 3) / 4 + i % g.mb_h] = 0;
+                fs->sse_part[(i / g.mb_h) * kSsePartStride + i % g.mb_h] = 0;
     }
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int mbi = blockIdx.x * 4 + wave;
@@ -2070,7 +2217,7 @@ __device__ void intra_p_mb(const Geometry& g, const FrameState* __restrict__ fs,
     }
     __syncthreads();  // both waves done: merge the chroma cbp
     const int nmb = g.mb_w * g.mb_h;
-    const int slot = (nmb + 3) / 4 + mby;
+    const int slot = mby;  // the row's delta (k_intra_analyze zeroed it): k_scan_rows adds it to the inter sums
     if (lane == 0) {
         if (wave == 0) {
             m.cbp = (uint8_t)((m.cbp & 15) | (m.cbp_c << 4));
@@ -2309,20 +2456,29 @@ __global__ __launch_bounds__(kScanThreads) void k_scan_rows(Geometry g, const Fr
                                                             const uint32_t* __restrict__ slot_bits,
                                                             uint4* __restrict__ row_agg,
                                                             unsigned long long* __restrict__ row_sse,
-                                                            const MbInfo* __restrict__ mbs, uint32_t* __restrict__ db_cnt) {
+                                                            const MbInfo* __restrict__ mbs, uint32_t* __restrict__ db_cnt,
+                                                            const uint32_t* __restrict__ mb_sse) {
     __shared__ int wi[kScanThreads / 64];
     __shared__ uint32_t wu[kScanThreads / 64];
     const int t = threadIdx.x, r = blockIdx.x, base = r * g.mb_w;
     const bool idr = fs->idr != 0;
-    // distortion partials of this row's share (one per intra MB row or per 4-MB inter workgroup,
-    // plus the per-row intra deltas of k_intra_wave / k_intra_p; one per MB row from k_db_sse
-    // when the in-loop filter is on)
+    // this row's distortion: its partial (k_intra_wave's in an I picture, k_db_sse's when the in-loop
+    // filter is on), or the per-macroblock sums the P coder left in mb_sse plus, with intra_in_p,
+    // k_intra_p's delta of the row
     const int nmb = g.mb_w * g.mb_h;
-    const int nparts = (idr || !fs->deblock_off) ? g.mb_h : (nmb + 3) / 4 + (fs->intra_in_p ? g.mb_h : 0);
-    const int p0 = (int)((long long)nparts * r / g.mb_h), p1 = (int)((long long)nparts * (r + 1) / g.mb_h);
+    const bool per_mb = !idr && fs->deblock_off;
     unsigned long long acc[4] = {0, 0, 0, 0};
-    for (int i = p0 + t; i < p1; i += kScanThreads)
-        for (int c = 0; c < 4; ++c) acc[c] += fs->sse_part[c * kSsePartStride + i];
+    if (per_mb) {
+        for (int j = t; j < g.mb_w; j += kScanThreads) {
+            const uint32_t sy = mb_sse[base + j];
+            acc[0] += sy;
+            acc[1] += mb_sse[nmb + base + j];
+            acc[2] += mb_sse[2 * nmb + base + j];
+            acc[3] += mb_unmasked(fs, j, r) ? sy : 0u;
+        }
+    }
+    if (t == 0 && (!per_mb || fs->intra_in_p))
+        for (int c = 0; c < 4; ++c) acc[c] += fs->sse_part[c * kSsePartStride + r];
     uint32_t b[kScanRowPer];
     int last = -1, first = 0x7fffffff;
     uint32_t ncoded = 0, over = 0;
@@ -2773,6 +2929,18 @@ void launch_inter(const Geometry& g, const DeviceBuffers& b, const uint8_t* src_
                        b.coef, b.mb_sse, b.wave_prog);
 }
 
+void launch_p_fused(const Geometry& g, const DeviceBuffers& b, const uint8_t* src_y, const uint8_t* src_uv,
+                    hipStream_t stream, const FrameState* publish) {
+    const int nmb = g.mb_w * g.mb_h;
+    StateArg sa{};
+    if (publish) sa.v = *publish;
+    sa.dst = b.fs;
+    sa.publish = publish ? 1 : 0;
+    sa.t_start = b.out_hdr ? &b.out_hdr->t_start : nullptr;
+    hipLaunchKernelGGL(k_p_fused, dim3(nmb), dim3(kMeThreads), 0, stream, g, sa, src_y, src_uv, b.mb, b.coef, b.mb_sse,
+                       b.wave_prog);
+}
+
 static void launch_analyze(const Geometry& g, const DeviceBuffers& b, const uint8_t* src_y, const uint8_t* src_uv,
                            hipStream_t stream, const FrameState* publish, bool first) {
     const int nmb = g.mb_w * g.mb_h;
@@ -2830,7 +2998,7 @@ void launch_entropy(const Geometry& g, const DeviceBuffers& b, uint8_t* host_out
     if (g.mb_h > kScanMaxRows || g.mb_w > kScanThreads * kScanRowPer)
         throw std::runtime_error("launch_entropy: frame too large for the row scan");
     hipLaunchKernelGGL(k_scan_rows, dim3(g.mb_h), dim3(kScanThreads), 0, stream, g, b.fs, b.slot_bits, b.row_agg,
-                       b.row_sse, b.mb, b.db_cnt);
+                       b.row_sse, b.mb, b.db_cnt, b.mb_sse);
     hipLaunchKernelGGL(k_scan_out, dim3(g.mb_h), dim3(kScanThreads), 0, stream, g, b.fs, b.slot_bits, b.row_agg,
                        b.row_sse, b.coded_info, b.slice_info, b.out_bytes, b.out_hdr, b.quad_unit, b.db_cnt);
     hipLaunchKernelGGL(k_pack, dim3(256), dim3(256), 0, stream, g, b.fs, b.slot, b.coded_info, b.slice_info,

@@ -306,6 +306,11 @@ MXHD bool drop_luma_for(int aq, uint32_t lsad, int tclass, int qp, long long d_p
         return tclass == kTcChanging && d_pred - d_coded < (long long)lambda_sse(qp) * (long long)bits;
     return drop_residual(aq, lsad, qp, d_pred, d_coded, bits);
 }
+// Whether drop_luma_for can return true at all for this macroblock: only then are its distortion
+// and bit-estimate arguments needed.
+MXHD bool drop_luma_possible(int aq, uint32_t lsad, int tclass) {
+    return aq >= 3 ? tclass == kTcChanging : (aq >= 2 && lsad > 256u * 32);
+}
 MXHD bool drop_chroma_for(int aq, int tclass, bool luma_dropped) {
     return luma_dropped || (aq >= 3 && tclass == kTcChanging);
 }
@@ -360,6 +365,53 @@ MXHD int luma_block_inter(const int* res, int qp, int* zscan, int* rres) {
     dequant4x4(z, d, qp, 0);
     idct4x4(d, rres);
     return nz;
+}
+
+// ---- residuals that are known to quantise to all-zero levels without running a transform
+// A coefficient of fdct4x4 is a sum of the block's 16 residuals with weights a(i) * a(j), a = 1 on
+// the even and 2 on the odd basis rows ({1,1,1,1}, {2,1,-1,-2}, {1,-1,-1,1}, {1,-2,2,-1}), so with
+// S = sum |residual| over the block, |coefficient (i, j)| <= a(i) a(j) S.  quant4x4 (inter dead
+// zone f) gives level 0 while |c| * MF + f < 2^qbits, hence every level of the block is 0 when
+// S <= min over the 16 positions of (2^qbits - 1 - f) / (a(i) a(j) MF[qp % 6][class]).  The
+// chroma DC coefficients of a plane are +-sums of its four blocks' DC terms (weight 1 each), so
+// they are bounded by the plane's sum over its 8x8 samples, against quant_dc_chroma's f and qbits.
+// A bound of 0 (low QPs) leaves only the all-zero block.  Sufficient, not necessary.
+constexpr int fdct_row_gain(int i) { return (i & 1) ? 2 : 1; }
+constexpr int zero_sum_4x4_calc(int qp) {
+    const int qm = qp % 6, qbits = 15 + qp / 6;
+    const int room = (1 << qbits) - 1 - (1 << qbits) / 6;  // quant4x4, inter
+    int t = room;
+    for (int i = 0; i < 16; ++i) {
+        const int b = room / (fdct_row_gain(i >> 2) * fdct_row_gain(i & 3) * kQuantMF[qm][kPosClass[i]]);
+        t = b < t ? b : t;
+    }
+    return t;
+}
+constexpr int zero_sum_chroma_dc_calc(int qpc) {
+    const int qm = qpc % 6, qbits = 16 + qpc / 6;
+    const int room = (1 << qbits) - 1 - 2 * ((1 << (qbits - 1)) / 6);  // quant_dc_chroma, inter
+    return room / kQuantMF[qm][0];
+}
+struct ZeroSumTab {
+    uint16_t blk[52], cdc[52];  // blk <= 16 * 255 matters, cdc <= 64 * 255: saturated to 16 bits
+    constexpr ZeroSumTab() : blk{}, cdc{} {
+        for (int q = 0; q < 52; ++q) {
+            const int a = zero_sum_4x4_calc(q), b = zero_sum_chroma_dc_calc(q);
+            blk[q] = (uint16_t)(a > 0xffff ? 0xffff : a);
+            cdc[q] = (uint16_t)(b > 0xffff ? 0xffff : b);
+        }
+    }
+};
+// Largest sum |residual| of an inter 4x4 block (luma at the macroblock's qp, chroma AC at its qpc)
+// for which every level is guaranteed 0.
+MXHD int zero_sum_4x4(int qp) {
+    constexpr ZeroSumTab tab;
+    return tab.blk[qp < 0 ? 0 : (qp > 51 ? 51 : qp)];
+}
+// Largest sum |residual| of an inter 8x8 chroma plane for which its four DC levels are guaranteed 0.
+MXHD int zero_sum_chroma_dc(int qpc) {
+    constexpr ZeroSumTab tab;
+    return tab.cdc[qpc < 0 ? 0 : (qpc > 51 ? 51 : qpc)];
 }
 
 // ME cost shared by both encoders.
