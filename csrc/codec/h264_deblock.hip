@@ -39,6 +39,7 @@
 #include <vector>
 
 #include "../common/hip_check.h"
+#include "../common/wave.h"
 #include "h264_deblock.h"
 #include "h264_gpu.h"
 #include "h264_mb.h"
@@ -117,28 +118,6 @@ struct DbShared {
     uint8_t cqp[52];                         // QP_C of a clipped qP_I (Table 8-15)
     uint8_t pad[R == 4 ? 20480 : 4];         // R 4: > 80 KiB, one deblocking workgroup per CU
 };
-template <int R>
-__device__ __forceinline__ int lds_cqp(const DbShared<R>& S, int qp, int offset) {
-    const int q = qp + offset;
-    return S.cqp[q < 0 ? 0 : (q > 51 ? 51 : q)];
-}
-template <int R>
-__device__ __forceinline__ DbParams lds_params(const DbShared<R>& S, int qpav) {
-    const uint32_t w = S.params[qpav < 0 ? 0 : (qpav > 51 ? 51 : qpav)];
-    DbParams d;
-    d.alpha = (int)(w & 0xff);
-    d.beta = (int)((w >> 8) & 31);
-    d.tc0 = w >> 13;
-    return d;
-}
-
-
-__device__ __forceinline__ void lds_sync_wave() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // LDS-only ordering: the ring hand-off never passes global data between waves of a workgroup, so
 // the progress words need no global-memory drain (a workgroup-scope release waits vmcnt(0) every
 // step, draining the prefetched lines and the pixel stores).
@@ -204,20 +183,6 @@ __device__ __forceinline__ uint4 rd_lane(const uint4& v, int j) {
                       (uint32_t)__builtin_amdgcn_readlane((int)v.z, j), (uint32_t)__builtin_amdgcn_readlane((int)v.w, j));
 }
 
-// 16-byte global load / store through address-space-1 pointers of a native vector type (a generic
-// access -- or one through HIP's uint4 class, whose copy constructor takes a generic reference --
-// compiles to flat_*, which also counts on lgkmcnt and so stalls every later LDS wait)
-typedef unsigned DbV4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(1))) DbV4 GDbV4;
-__device__ __forceinline__ uint4 gld16(const uint8_t* p) {
-    const DbV4 v = *(const GDbV4*)p;
-    return make_uint4(v.x, v.y, v.z, v.w);
-}
-__device__ __forceinline__ void gst16(uint8_t* p, const uint4& v) {
-    const DbV4 d = {v.x, v.y, v.z, v.w};
-    *(GDbV4*)p = d;
-}
-
 // bounded spin until *p >= need (LDS, same workgroup); false on timeout
 __device__ __forceinline__ bool wait_lds(const int* p, int need, int* err) {
     for (unsigned s = 0; lds_load(p) < need; ++s) {
@@ -230,18 +195,6 @@ __device__ __forceinline__ bool wait_lds(const int* p, int need, int* err) {
     __atomic_signal_fence(__ATOMIC_SEQ_CST);
     return true;
 }
-__device__ __forceinline__ void unpack16(const uint4& v, int* o) {
-    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (int k = 0; k < 16; ++k) o[k] = (w[k >> 2] >> (8 * (k & 3))) & 0xff;
-}
-__device__ __forceinline__ uint4 pack16(const int* o) {
-    uint32_t w[4] = {0, 0, 0, 0};
-#pragma unroll
-    for (int k = 0; k < 16; ++k) w[k >> 2] |= (uint32_t)(o[k] & 0xff) << (8 * (k & 3));
-    return make_uint4(w[0], w[1], w[2], w[3]);
-}
-
 // QP_Y entering row `mby` (P pictures, one slice: the last dqp MB of an earlier row, else the slice QP)
 __device__ __forceinline__ int row_entry_qp(const FrameState* fs, const int* row_lastq, int mby, int lane) {
     if (fs->idr) return fs->qp;
@@ -601,7 +554,7 @@ __device__ void db_luma_row(const Geometry& g, const FrameState* fs, const uint4
             }
             *reinterpret_cast<uint32_t*>(&tile[4 + r][4 * e]) = cur;
             const DbParams dt = spar(T, (qtop + qp + 1) >> 1);
-            lds_sync_wave();
+            wave_lds_sync();
             Px8 in;
             in.p3 = tile[4 * e][r];
             in.p2 = tile[4 * e + 1][r];
@@ -616,7 +569,7 @@ __device__ void db_luma_row(const Geometry& g, const FrameState* fs, const uint4
             const bool internal = ((rr.z >> 12) | (rr.w & 0xffffffu)) != 0;
             const bool strong0 = __any(e == 0 && bs == 4);
             const Px8 o = settle_edges(in, bs, sel_params(e == 0, dt, dq), e, edge_passes(internal, strong0));
-            lds_sync_wave();  // every lane's reads done before the tile is rewritten
+            wave_lds_sync();  // every lane's reads done before the tile is rewritten
             // Each lane writes rows no other lane writes (the compiler may reorder one lane's stores,
             // so lanes must not race on a byte): edge e's q0' / q1' (rows 4e+4, 4e+5) and p1' / p0'
             // (rows 4e+2, 4e+3).  Edge e's q2' is edge e+1's p1 input, which that edge's p1' already
@@ -627,7 +580,7 @@ __device__ void db_luma_row(const Geometry& g, const FrameState* fs, const uint4
             if (strong0 && e == 0) tile[1][r] = (uint8_t)o.p2;
             tile[4 * e + 2][r] = (uint8_t)o.p1;
             tile[4 * e + 3][r] = (uint8_t)o.p0;
-            lds_sync_wave();
+            wave_lds_sync();
             cur = *reinterpret_cast<const uint32_t*>(&tile[4 + r][4 * e]);
             // the upper neighbour's rows 13..15: this row is their writer when it filters its top edge
             if (t0 && r >= 1 && r < 4)
@@ -791,7 +744,7 @@ __device__ void db_chroma_row(const Geometry& g, const FrameState* fs, const uin
             }
             if (comp == 0) *reinterpret_cast<uint32_t*>(&tile[2 + k][4 * dq4]) = cur;
             const DbParams dt = spar(T, (scqp(T, qtop, cqo) + cq + 1) >> 1);
-            lds_sync_wave();
+            wave_lds_sync();
             const bool hl = lane < 32;
             const int r0 = 4 * hce;  // tile rows r0 .. r0+3 = p1, p0, q0, q1
             int p1 = tile[r0][hb], p0 = tile[r0 + 1][hb], q0 = tile[r0 + 2][hb];
@@ -799,17 +752,17 @@ __device__ void db_chroma_row(const Geometry& g, const FrameState* fs, const uin
             const uint32_t b4 = hce ? he2 : t0;
             const int bs = hl ? (int)((b4 >> (3 * (hb >> 2))) & 7u) : 0;
             db_chroma_line(p1, p0, q0, q1, bs, sel_params(hce == 0, dt, dq));
-            lds_sync_wave();
+            wave_lds_sync();
             if (hl) {
                 tile[r0 + 1][hb] = (uint8_t)p0;
                 tile[r0 + 2][hb] = (uint8_t)q0;
             }
-            lds_sync_wave();
+            wave_lds_sync();
             cur = *reinterpret_cast<const uint32_t*>(&tile[2 + k][4 * dq4]);
             if (t0 && lane < 4)  // the upper neighbour's row 7
                 gst4(UV + (size_t)(mby * 8 - 1) * pitch + 16 * x + 4 * lane,
                      *reinterpret_cast<const uint32_t*>(&tile[1][4 * lane]));
-            lds_sync_wave();
+            wave_lds_sync();
         }
         if (!band_first && lane == 0) lds_publish(cons_me, x + 1);
         prev = cur;

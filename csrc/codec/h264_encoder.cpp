@@ -334,7 +334,6 @@ GpuH264Encoder::GpuH264Encoder(const EncoderConfig& cfg, hipStream_t stream)
     geom_.pitch = (geom_.coded_w + 255) & ~255;
     if (geom_.mb_h > kMaxSlices) throw std::invalid_argument("picture too tall");
     if (geom_.mb_w > 512) throw std::invalid_argument("picture too wide (k_intra_wave stages <= 512 MBs per row)");
-    const int nmb = geom_.mb_w * geom_.mb_h;
     if (geom_.mb_h > kSsePartStride)
         throw std::invalid_argument("frame too large for the distortion partials");
     const size_t ysz = (size_t)geom_.pitch * geom_.coded_h, uvsz = ysz / 2;

@@ -3,11 +3,11 @@
 // Per-frame kernel chain (all on one HIP stream, graph-capturable):
 //   P frame: k_p_fused (or k_me_full -> k_inter_encode when the search runs on the unfiltered
 //            copy of a deblocked reference) -> k_intra_analyze -> k_intra_p (intra_in_p)
-//            -> k_cavlc -> k_scan -> k_pack
+//            -> k_cavlc -> k_scan_rows -> k_scan_out -> k_pack
 // Both P-frame kernels interpolate the reference's sub-sample positions themselves, from windows of
 // the reconstruction staged in LDS (the HEVC and VP8 encoders still build k_hpel's planes for
 // their prediction kernels).
-//   I frame: k_intra_analyze -> k_intra_wave -> k_cavlc -> k_scan -> k_pack
+//   I frame: k_intra_analyze -> k_intra_wave -> k_cavlc -> k_scan_rows -> k_scan_out -> k_pack
 // k_intra_analyze decides every macroblock's intra modes open-loop (SATD against predictions
 // from source neighbours, fully parallel); k_intra_wave reconstructs the intra macroblocks
 // closed-loop in a diagonal wavefront (one luma and one chroma wave per MB row).
@@ -105,7 +105,7 @@ struct FrameState {
     // (profiles/r06_deblock) -- nullptr: ref_y
     const uint8_t* me_ref;
     // distortion partials (Y, U, V, Y outside the mask MBs) over the display area, [4][kSsePartStride]: one per
-    // MB row (k_intra_wave, k_db_sse, k_intra_p's deltas), reduced by k_scan into OutHeader; the P coder
+    // MB row (k_intra_wave, k_db_sse, k_intra_p's deltas), reduced by k_scan_rows / k_scan_out into OutHeader; the P coder
     // leaves its sums per macroblock in DeviceBuffers::mb_sse and k_scan_rows adds up its row's
     unsigned long long* sse_part;
 };

@@ -19,7 +19,8 @@
 //  * k_cavlc        one wave per macroblock: lane 0 codes the MB header (P_Skip decision,
 //                   median mv prediction, cbp), lanes 1..27 code one residual block each;
 //                   a wave prefix-sum places every lane's bits in an LDS slot.
-//  * k_scan         one workgroup: skip runs, per-MB and per-slice bit offsets.
+//  * k_scan_rows / k_scan_out  one workgroup per MB row, two passes: skip runs, per-MB and
+//                   per-slice bit offsets, the frame's distortion.
 //  * k_pack         one thread per output word gathers the overlapping header / MB /
 //                   trailer bits and stores the word straight into pinned host memory.
 #include <hip/hip_runtime.h>
@@ -27,6 +28,7 @@
 #include <cstddef>
 
 #include "../common/hip_check.h"
+#include "../common/wave.h"
 #include "h264_core.h"
 #include "h264_deblock.h"
 #include "h264_gpu.h"
@@ -38,72 +40,6 @@ namespace h264 {
 namespace {
 
 __device__ __forceinline__ uint32_t bswap32(uint32_t v) { return __builtin_bswap32(v); }
-
-// Bit writer that ORs 32-bit chunks into a zero-initialised word array starting at an
-// arbitrary bit offset (atomicOr: neighbouring writers share boundary words).
-template <bool kSwap>
-struct OrWriter {
-    uint32_t* dst;
-    uint32_t pos;  // absolute bit position of the next chunk
-    uint64_t acc;
-    int nacc;
-    uint32_t bits;
-
-    __device__ __forceinline__ void init(uint32_t* d, uint32_t bitpos) {
-        dst = d;
-        pos = bitpos;
-        acc = 0;
-        nacc = 0;
-        bits = 0;
-    }
-    __device__ __forceinline__ void emit(uint32_t w, int n) {  // w: n valid bits left-aligned
-        const uint32_t wi = pos >> 5, sh = pos & 31;
-        uint32_t a = w >> sh;
-        if (a) atomicOr(dst + wi, kSwap ? bswap32(a) : a);
-        if (sh && n > (int)(32 - sh)) {
-            uint32_t b2 = w << (32 - sh);
-            if (b2) atomicOr(dst + wi + 1, kSwap ? bswap32(b2) : b2);
-        }
-        pos += n;
-    }
-    __device__ __forceinline__ void put(uint32_t v, int n) {
-        if (n <= 0) return;
-        uint64_t m = (n == 32) ? 0xffffffffull : ((1ull << n) - 1);
-        acc = (acc << n) | (v & m);
-        nacc += n;
-        bits += n;
-        if (nacc >= 32) {
-            emit((uint32_t)(acc >> (nacc - 32)), 32);
-            nacc -= 32;
-        }
-    }
-    __device__ __forceinline__ void flush() {
-        if (nacc > 0) {
-            emit((uint32_t)(acc << (32 - nacc)), nacc);
-            nacc = 0;
-            acc = 0;
-        }
-    }
-};
-
-// Sum of the four rows of 16 lanes, every lane gets it (whole wave active): v_permlane16_swap
-// and v_permlane32_swap with both operands = v leave {v, v ^ 16} (then {v, v ^ 32}) on every
-// lane, so the pair sum is the xor-16 / xor-32 butterfly step without a ds_bpermute round trip.
-__device__ __forceinline__ uint32_t rows_sum(uint32_t v) {
-    const auto r16 = __builtin_amdgcn_permlane16_swap(v, v, false, false);
-    v = r16[0] + r16[1];
-    const auto r32 = __builtin_amdgcn_permlane32_swap(v, v, false, false);
-    return r32[0] + r32[1];
-}
-// Wave sum, every lane gets it (whole wave active): quad and row-of-16 sums with DPP
-// (quad_perm [1,0,3,2], [2,3,0,1], row_ror 4, row_ror 8), then rows_sum.
-__device__ __forceinline__ int wave_sum(int v) {
-    v += __builtin_amdgcn_mov_dpp(v, 0xB1, 0xF, 0xF, false);
-    v += __builtin_amdgcn_mov_dpp(v, 0x4E, 0xF, 0xF, false);
-    v += __builtin_amdgcn_mov_dpp(v, 0x124, 0xF, 0xF, false);
-    v += __builtin_amdgcn_mov_dpp(v, 0x128, 0xF, 0xF, false);
-    return (int)rows_sum((uint32_t)v);
-}
 
 // ------------------------------------------------------------------ half-pel planes
 // LDS-tiled F/H/V/J plane builder, 128x16 output tile per 256-thread workgroup.
@@ -144,6 +80,16 @@ __device__ __forceinline__ void publish_state(const StateArg& a) {
         reinterpret_cast<uint32_t*>(a.dst)[threadIdx.x] = reinterpret_cast<const uint32_t*>(&a.v)[threadIdx.x];
 }
 __device__ __forceinline__ const FrameState& state_of(const StateArg& a) { return a.publish ? a.v : *a.dst; }
+// Host side: the argument of a launch.  publish: the state to pass by value, or nullptr to read
+// b.fs; stamp: this kernel is the picture's first and records OutHeader::t_start.
+inline StateArg make_state_arg(const DeviceBuffers& b, const FrameState* publish, bool stamp = true) {
+    StateArg sa{};
+    if (publish) sa.v = *publish;
+    sa.dst = b.fs;
+    sa.publish = publish ? 1 : 0;
+    sa.t_start = (b.out_hdr && stamp) ? &b.out_hdr->t_start : nullptr;
+    return sa;
+}
 
 __global__ __launch_bounds__(256) void k_hpel(Geometry g, StateArg sa, uint8_t* __restrict__ pf,
                                               uint8_t* __restrict__ ph, uint8_t* __restrict__ pv,
@@ -770,12 +716,6 @@ __global__ __launch_bounds__(kMeThreads) void k_me_full_val(Geometry g, StateArg
 // broadcasts (no LDS round trips); the integer arithmetic is exactly fdct4x4 / idct4x4 /
 // hadamard4x4 / quant4x4 / dequant4x4 (rows first, then columns), so the bitstream is
 // unchanged.  A block-per-lane layout left 40 of 64 lanes idle in the transform phase.
-template <int K>
-__device__ __forceinline__ int qbc(int v) {  // lane K of this lane's quad (quad_perm [K,K,K,K])
-    return __builtin_amdgcn_mov_dpp(v, K * 0x55, 0xF, 0xF, false);
-}
-__device__ __forceinline__ int quad_sum(int v) { return qbc<0>(v) + qbc<1>(v) + qbc<2>(v) + qbc<3>(v); }
-
 // forward core transform of row r of a block whose rows sit in the quad: y = row r of Cf X Cf^T
 __device__ __forceinline__ void fdct_row(const int* x, int r, int* y) {
     const int s03 = x[0] + x[3], d03 = x[0] - x[3], s12 = x[1] + x[2], d12 = x[1] - x[2];
@@ -838,12 +778,6 @@ __device__ __forceinline__ void dequant_row(const int* z, int r, int qp, int* d)
     for (int c = 0; c < 4; ++c) d[c] = z[c] * kDequantV[qm][kPosClass[r * 4 + c]] * (1 << qs);
 }
 
-__device__ __forceinline__ void wave_sync_lds() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // Quarter-sample luma prediction of one macroblock straight from the reference picture (8.4.2.2.1;
 // sample for sample luma_qpel() of the CPU encoder), by one wave.  The macroblock has n = 1 or 2
 // vectors (partitions); (xa, ya) and (xb, yb) are the quarter-sample positions its top-left sample
@@ -874,7 +808,7 @@ __device__ __forceinline__ void mc_luma_wave(uint32_t* __restrict__ w, const uin
         }
         w[i] = v;
     }
-    wave_sync_lds();
+    wave_lds_sync();
     {
         const int xf = (lpi ? xb : xa) & 3, yf = (lpi ? yb : ya) & 3;
         w += lpi * kMcWords;
@@ -962,7 +896,7 @@ struct InterLds {
 // One P macroblock coded by one wave (whole wave active): prediction under the motion `mi`
 // (mvx / mvy / part / pmv), residual, transforms or their shortcuts, reconstruction, the rest of
 // MbInfo and the macroblock's distortion (mb_sse[c * nmb + mbi], c = Y, U, V: k_scan_rows sums
-// them).  L is the wave's own; it synchronises with wave_sync_lds() only.
+// them).  L is the wave's own; it synchronises with wave_lds_sync() only.
 __device__ __forceinline__ void inter_code_mb(const Geometry& g, const CodeState& fs, const uint8_t* __restrict__ src_y,
                                               const uint8_t* __restrict__ src_uv, MbInfo* __restrict__ mbs,
                                               int16_t* __restrict__ coef, uint32_t* __restrict__ mb_sse, int mbi,
@@ -1093,7 +1027,7 @@ __device__ __forceinline__ void inter_code_mb(const Geometry& g, const CodeState
             L.res[256 + comp * 64 + lane] = (int16_t)crs[comp];
         }
     }
-    wave_sync_lds();
+    wave_lds_sync();
 
     // ---- luma: lane = 4 * blkIdx + row
     const int lb = lane >> 2, rr = lane & 3, lbx = kBlkX[lb], lby = kBlkY[lb];
@@ -1208,7 +1142,7 @@ __device__ __forceinline__ void inter_code_mb(const Geometry& g, const CodeState
             }
             if (rr == 0) (ccomp ? mbs[mbi].nz_cr : mbs[mbi].nz_cb)[cblk] = (uint8_t)nzc;
         }
-        wave_sync_lds();
+        wave_lds_sync();
         if ((lane == 0 || lane == 16)) {
             const int comp = lane >> 4;
             int in[4], zd[4], dq[4];
@@ -1219,7 +1153,7 @@ __device__ __forceinline__ void inter_code_mb(const Geometry& g, const CodeState
             for (int i = 0; i < 4; ++i) L.cdc[comp * 4 + i] = dq[i];
             L.cdc_nz[comp] = n;
         }
-        wave_sync_lds();
+        wave_lds_sync();
         if (clane) {
             int d[4], cr[4];
             dequant_row(cz, rr, qpc, d);
@@ -1349,7 +1283,7 @@ __global__ __launch_bounds__(256) void k_intra_analyze(Geometry g, StateArg sa, 
         const int r = i / 18, bx = i - r * 18, x = x0 - 2 + bx, y = y0 / 2 - 1 + r;
         ctile[wave][r][bx] = (x >= 0 && y >= 0) ? src_uv[y * g.pitch + x] : 0;
     }
-    wave_sync_lds();
+    wave_lds_sync();
     const uint8_t* sy = &ltile[wave][1][1];
     const uint8_t* suv = &ctile[wave][1][2];
     IntraCosts& c = costs[wave];
@@ -1430,9 +1364,7 @@ __global__ __launch_bounds__(256) void k_intra_analyze(Geometry g, StateArg sa, 
             if (lane == 0) c.cc[m] = ok ? t : kCostInf;
         }
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
     if (lane == 0) {
         const IntraDecision d = decide_intra(c, fs->qp, fs->intra4x4 != 0);
         MbInfo& m = mbs[mbi];
@@ -1676,7 +1608,7 @@ __device__ void intra_luma_mb(const Geometry& g, const MbFields& f, const uint32
             const unsigned long long any = __ballot(rb >= 0 && r == 0 && nzb > 0);
             for (int gq = 0; gq < 2; ++gq)
                 if ((any >> (4 * gq)) & 1ull) cbp_l |= 1 << (raster_to_blk(i4_step_block(t, gq)) >> 2);
-            wave_sync_lds();
+            wave_lds_sync();
         }
     } else {  // Intra16x16
         const NbMb n = nbmb_from_plane(tile, kLT, 0, 0, 16, 1, 0, av.left, av.top, av.topleft);
@@ -1692,7 +1624,7 @@ __device__ void intra_luma_mb(const Geometry& g, const MbFields& f, const uint32
         const int nz = quad_sum(quant_row_i(y, r, T, 1, z));
 #pragma unroll
         for (int c = 0; c < 4; ++c) mc[kCoefLuma + b * 16 + zz_inv(r * 4 + c)] = (int16_t)z[c];
-        wave_sync_lds();
+        wave_lds_sync();
         if (lane < 4) {  // DC matrix row `lane`: Hadamard, /2, quantise (quant_dc_luma), then dequant_dc_luma
             int dc[4], h[4], zd[4], fh[4];
 #pragma unroll
@@ -1715,7 +1647,7 @@ __device__ void intra_luma_mb(const Geometry& g, const MbFields& f, const uint32
                 ldc[lane * 4 + c] = f.qp >= 36 ? fh[c] * ls16 * (1 << (T.qs - 6))
                                                : (fh[c] * ls16 + (1 << (5 - T.qs))) >> (6 - T.qs);
         }
-        wave_sync_lds();
+        wave_lds_sync();
         const bool luma_ac = __ballot(r == 0 && nz > 0) != 0;
         int d[4], rr[4];
         dequant_row_t(z, r, T, d);
@@ -1731,7 +1663,7 @@ __device__ void intra_luma_mb(const Geometry& g, const MbFields& f, const uint32
         }
         if (r == 0) m.nz_luma[by * 4 + bx] = (uint8_t)(luma_ac ? nz : 0);
         cbp_l = luma_ac ? 15 : 0;
-        wave_sync_lds();
+        wave_lds_sync();
     }
     if (lane == 0) m.cbp = (uint8_t)cbp_l;  // chroma bits merged at the end of the row
 }
@@ -1768,7 +1700,7 @@ __device__ void intra_chroma_mb(const Geometry& g, int chroma_qp_offset, const M
             if (r * 4 + c > 0) mc[kCoefChromaAc + (comp * 4 + cb) * 16 + zz_inv(r * 4 + c)] = (int16_t)z[c];
         if (r == 0) (comp ? m.nz_cr : m.nz_cb)[cb] = (uint8_t)nz;
     }
-    wave_sync_lds();
+    wave_lds_sync();
     int ndc = 0;
     if (lane == 0 || lane == 16) {
         const int cp = lane >> 4;
@@ -1779,7 +1711,7 @@ __device__ void intra_chroma_mb(const Geometry& g, int chroma_qp_offset, const M
         dequant_dc_chroma(zd, dq, qpc);
         for (int i = 0; i < 4; ++i) cdc[cp * 4 + i] = dq[i];
     }
-    wave_sync_lds();
+    wave_lds_sync();
     const bool any_ac = __ballot(clane && nz > 0) != 0, any_dc = __ballot(ndc > 0) != 0;
     if (clane) {
         int d[4], rr[4];
@@ -1802,7 +1734,7 @@ __device__ void intra_chroma_mb(const Geometry& g, int chroma_qp_offset, const M
             sse_u += s;
     }
     if (lane == 0) m.cbp_c = (uint8_t)(any_ac ? 2 : (any_dc ? 1 : 0));
-    wave_sync_lds();
+    wave_lds_sync();
 }
 
 
@@ -1815,36 +1747,31 @@ __device__ void intra_chroma_mb(const Geometry& g, int chroma_qp_offset, const M
 // so a reader that sees the counter sees the line.  The cross-CU version of this hand-off
 // (tagged L2-bypassing line words between per-row workgroups) spent most of its time waiting
 // for the stores to become visible (profiles/r02_idr).
-struct IntraWaveTiles {
-    uint8_t lt[17][kLT];    // luma tile: row 0 = top neighbours, column 0 = left neighbours
-    uint8_t ct[2][9][kCT];  // chroma tiles (Cb, Cr)
-    uint32_t src[64];       // source of the current MB (luma 16 x 16 / chroma 8 rows x 16 bytes)
-    int dc[16];             // luma DC / chroma DC scratch
+struct ChromaWaveTiles {
+    uint8_t ct[2][9][kCT];  // chroma tiles (Cb, Cr): row 0 = top neighbours, column 0 = left neighbours
+    uint32_t src[64];       // source of the current MB (8 rows x 16 interleaved bytes, lanes 0..31)
+    int dc[16];             // chroma DC scratch
 };
 
-// One plane's rows of the slice.
-template <bool chroma>
-__device__ __forceinline__ void intra_wave_rows(const Geometry& g, const FrameState* __restrict__ fs,
-                                             const uint8_t* __restrict__ src_y, const uint8_t* __restrict__ src_uv,
-                                             MbInfo* __restrict__ mbs, int16_t* __restrict__ coef, uint8_t* s_line,
-                                             IntraWaveTiles* tiles, int* prog) {
+// The chroma rows of the slice, one macroblock at a time.
+__device__ __forceinline__ void intra_chroma_rows(const Geometry& g, const FrameState* __restrict__ fs,
+                                                  const uint8_t* __restrict__ src_uv, MbInfo* __restrict__ mbs,
+                                                  int16_t* __restrict__ coef, uint8_t* s_line,
+                                                  ChromaWaveTiles* tiles, int* prog) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int slice_rows = fs->slice_rows, cqp_off = fs->chroma_qp_offset;
-    uint8_t* const rec_y = fs->rec_y;
     uint8_t* const rec_uv = fs->rec_uv;
     const int mby = blockIdx.x * slice_rows + wave;
     const bool active = mby < g.mb_h;  // the last slice may be shorter (whole waves)
     if (!active) return;  // no workgroup barriers below
-    IntraWaveTiles& T = tiles[wave];
+    ChromaWaveTiles& T = tiles[wave];
     uint8_t* my_line = s_line + (size_t)wave * g.coded_w;
     const uint8_t* up_line = s_line + (size_t)(wave > 0 ? wave - 1 : 0) * g.coded_w;
-    uint32_t sse_a = 0, sse_b = 0;  // luma: Y; chroma: U, V
-    uint32_t sse_m = 0;             // luma: Y of the MBs outside the quality-report mask
+    uint32_t sse_a = 0, sse_b = 0;  // U, V
     // software pipeline: the next MB's source dword and fields load while this one is coded
     auto fetch_src = [&](int mbx) -> uint32_t {
         if (mbx >= g.mb_w) return 0u;
         const int r = lane >> 2, c4 = (lane & 3) * 4;
-        if (!chroma) return *reinterpret_cast<const uint32_t*>(src_y + (size_t)(mby * 16 + r) * g.pitch + mbx * 16 + c4);
         if (lane >= 32) return 0u;
         return *reinterpret_cast<const uint32_t*>(src_uv + (size_t)(mby * 8 + r) * g.pitch + mbx * 16 + c4);
     };
@@ -1863,33 +1790,12 @@ __device__ __forceinline__ void intra_wave_rows(const Geometry& g, const FrameSt
         const Avail av = mb_avail(g, mbx, mby, slice_rows);
         int16_t* mc = coef + (size_t)mbi * kCoefStride;
         if (av.top) {  // wait for the row above (uniform)
-            const int need = chroma ? mbx + 1 : (av.topright ? mbx + 2 : mbx + 1);
+            const int need = mbx + 1;
             while (__hip_atomic_load(&prog[wave - 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < need)
                 __builtin_amdgcn_s_sleep(1);
             __atomic_signal_fence(__ATOMIC_SEQ_CST);
         }
-        if (!chroma) {
-            const int x0 = mbx * 16, y0 = mby * 16;
-            // the left column is the previous MB's right column, already in the tile
-            const uint8_t keep = lane < 16 ? T.lt[1 + lane][16] : 0;
-            const int x = x0 - 1 + lane;
-            const bool need = lane < 21 && (lane == 0 ? av.topleft : (lane <= 16 ? av.top : av.topright));
-            const uint8_t top = need ? up_line[x] : 0;
-            wave_sync_lds();
-            if (lane < 16) T.lt[1 + lane][0] = av.left ? keep : 0;
-            if (lane < 21) T.lt[0][lane] = top;
-            wave_sync_lds();
-            uint32_t sse_mb = 0;
-            intra_luma_mb(g, f, T.src, m, mc, mbx, mby, av, T.lt, T.dc, lane, sse_mb);
-            sse_a += sse_mb;
-            if (mb_unmasked(fs, mbx, mby)) sse_m += sse_mb;
-            // tile -> reconstruction: 16 rows x 16 bytes, one dword per lane; bottom line -> LDS
-            const int r = lane >> 2, c4 = (lane & 3) * 4;
-            const uint32_t v = (uint32_t)T.lt[1 + r][1 + c4] | ((uint32_t)T.lt[1 + r][2 + c4] << 8) |
-                               ((uint32_t)T.lt[1 + r][3 + c4] << 16) | ((uint32_t)T.lt[1 + r][4 + c4] << 24);
-            *reinterpret_cast<uint32_t*>(rec_y + (size_t)(y0 + r) * g.pitch + x0 + c4) = v;
-            if (r == 15) *reinterpret_cast<uint32_t*>(my_line + x0 + c4) = v;
-        } else {
+        {
             const int xc0 = mbx * 8, yc0 = mby * 8;
             uint8_t keep = 0;
             if (lane < 16) keep = T.ct[lane >> 3][1 + (lane & 7)][8];
@@ -1898,12 +1804,12 @@ __device__ __forceinline__ void intra_wave_rows(const Geometry& g, const FrameSt
             const int x = 2 * (xc0 - 1 + cx) + comp_t;
             const bool need = lane >= 16 && lane < 34 && (cx == 0 ? av.topleft : av.top);
             const uint8_t top = need ? up_line[x] : 0;
-            wave_sync_lds();
+            wave_lds_sync();
             if (lane < 16)
                 T.ct[lane >> 3][1 + (lane & 7)][0] = av.left ? keep : 0;
             else if (lane < 34)
                 T.ct[comp_t][0][cx] = top;
-            wave_sync_lds();
+            wave_lds_sync();
             intra_chroma_mb(g, cqp_off, f, T.src, m, mc, mbx, mby, av, T.ct, T.dc, lane, sse_a, sse_b);
             if (lane < 32) {  // 8 rows x 16 interleaved bytes, one dword (2 samples x 2 planes) per lane
                 const int r = lane >> 2, c2 = (lane & 3) * 2;
@@ -1919,23 +1825,17 @@ __device__ __forceinline__ void intra_wave_rows(const Geometry& g, const FrameSt
     }
 #ifdef MX_IDR_TIMING
     if (lane == 0)
-        printf("MXIDR plane %d slice %d row %d wall_ticks %llu\n", (int)chroma, (int)blockIdx.x, wave, wall_clock64() - t_start);
+        printf("MXIDR plane 1 slice %d row %d wall_ticks %llu\n", (int)blockIdx.x, wave, wall_clock64() - t_start);
 #endif
     // distortion of the row (one partial per row and channel)
-    unsigned long long a = sse_a, b = sse_b, mm = sse_m;
+    unsigned long long a = sse_a, b = sse_b;
     for (int o = 32; o > 0; o >>= 1) {
         a += __shfl_xor(a, o, 64);
         b += __shfl_xor(b, o, 64);
-        mm += __shfl_xor(mm, o, 64);
     }
     if (lane == 0) {
-        if (!chroma) {
-            fs->sse_part[0 * kSsePartStride + mby] = a;
-            fs->sse_part[3 * kSsePartStride + mby] = mm;
-        } else {
-            fs->sse_part[1 * kSsePartStride + mby] = a;
-            fs->sse_part[2 * kSsePartStride + mby] = b;
-        }
+        fs->sse_part[1 * kSsePartStride + mby] = a;
+        fs->sse_part[2 * kSsePartStride + mby] = b;
     }
 }
 
@@ -1992,10 +1892,10 @@ __device__ __forceinline__ void intra_luma_rows_pl(const Geometry& g, const Fram
         const uint8_t top = need ? up_line[x * 16 - 1 + lane] : 0;
         uint8_t lft = 0;
         if (left && lane < 16 && av.left) lft = P.lt[(x + 2) % 3][1 + lane][16];
-        wave_sync_lds();
+        wave_lds_sync();
         if (lane < 21) P.lt[j][0][lane] = top;
         if (left && lane < 16) P.lt[j][1 + lane][0] = lft;
-        wave_sync_lds();
+        wave_lds_sync();
     };
     // MB x is complete: tile -> reconstruction, bottom line -> LDS, then publish it
     auto finish = [&](int x) {
@@ -2079,7 +1979,7 @@ __device__ __forceinline__ void intra_luma_rows_pl(const Geometry& g, const Fram
                 if (r == 0) mbs[mbi].nz_luma[rb] = (uint8_t)nzb;
             }
             const unsigned long long any = __ballot(rb >= 0 && r == 0 && nzb > 0);
-            wave_sync_lds();
+            wave_lds_sync();
             // per slot (uniform): coded-block bits, right-column hand-off, completion
 #pragma unroll
             for (int s = 0; s < 3; ++s) {
@@ -2097,7 +1997,7 @@ __device__ __forceinline__ void intra_luma_rows_pl(const Geometry& g, const Fram
                     finish(base + ks);
                 }
             }
-            wave_sync_lds();
+            wave_lds_sync();
         }
         next = base + started;
     }
@@ -2122,7 +2022,7 @@ __global__ __launch_bounds__(512) void k_intra_wave(Geometry g, const FrameState
     // a serial chain on few waves: issue priority over the bulk kernels sharing its SIMDs
     __builtin_amdgcn_s_setprio(3);
     extern __shared__ uint8_t s_line[];  // [slice rows][coded_w]: bottom sample line of every coded MB
-    __shared__ IntraWaveTiles tiles[8];     // chroma workgroups
+    __shared__ ChromaWaveTiles tiles[8];    // chroma workgroups
     __shared__ LumaPipeTiles ltiles[8];     // luma workgroups
     __shared__ int prog[8];              // macroblocks of the row whose bottom line is in s_line
     if ((threadIdx.x & 63) == 0) prog[threadIdx.x >> 6] = 0;
@@ -2130,7 +2030,7 @@ __global__ __launch_bounds__(512) void k_intra_wave(Geometry g, const FrameState
     if (blockIdx.y == 0)
         intra_luma_rows_pl(g, fs, src_y, mbs, coef, s_line, ltiles, prog);
     else
-        intra_wave_rows<true>(g, fs, src_y, src_uv, mbs, coef, s_line, tiles, prog);
+        intra_chroma_rows(g, fs, src_uv, mbs, coef, s_line, tiles, prog);
 }
 
 // IDR: luma and chroma coded bits merged into the MB's cbp once both planes are done.
@@ -2181,7 +2081,7 @@ __device__ void intra_p_mb(const Geometry& g, const FrameState* __restrict__ fs,
             const bool ok = lane == 0 ? av.topleft : (lane <= 16 ? av.top : av.topright);
             lt[0][lane] = ok ? fs->rec_y[(y0 - 1) * g.pitch + x0 - 1 + lane] : 0;
         }
-        wave_sync_lds();
+        wave_lds_sync();
         intra_luma_mb(g, f, ls, m, mc, mbx, mby, av, lt, ldc, lane, s0);
         const int r = lane >> 2, c4 = (lane & 3) * 4;
         const uint32_t v = (uint32_t)lt[1 + r][1 + c4] | ((uint32_t)lt[1 + r][2 + c4] << 8) |
@@ -2201,7 +2101,7 @@ __device__ void intra_p_mb(const Geometry& g, const FrameState* __restrict__ fs,
             const bool ok = cx == 0 ? av.topleft : av.top;
             ct[comp][0][cx] = ok ? fs->rec_uv[(yc0 - 1) * g.pitch + 2 * (xc0 - 1 + cx) + comp] : 0;
         }
-        wave_sync_lds();
+        wave_lds_sync();
         intra_chroma_mb(g, fs->chroma_qp_offset, f, cs, m, mc, mbx, mby, av, ct, cdc, lane, s0, s1);
         if (lane < 32) {
             const int r = lane >> 2, c2 = (lane & 3) * 2;
@@ -2296,9 +2196,7 @@ __global__ __launch_bounds__(256) void k_cavlc(Geometry g, const FrameState* __r
             const int k = q / kW, d = q - k * kW;
             if (ok[k]) reinterpret_cast<uint32_t*>(&nbuf[wave][k])[d] = reinterpret_cast<const uint32_t*>(&mbs[src[k]])[d];
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_sync();
     }
     const MbNbrs nb{&nbuf[wave][0], &nbuf[wave][1], &nbuf[wave][2], &nbuf[wave][3], &nbuf[wave][4]};
     const MbInfo& m = nbuf[wave][0];
@@ -2352,9 +2250,7 @@ __global__ __launch_bounds__(256) void k_cavlc(Geometry g, const FrameState* __r
         uint4* dst = reinterpret_cast<uint4*>(cbuf[wave]);
         for (int q = lane; q < kCoefStride / 8; q += 32) dst[q] = src[q];
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
     uint32_t bits = 0;
     if (!skip && lane < kNumRoles) {
         BitWriter w;
@@ -2375,9 +2271,7 @@ __global__ __launch_bounds__(256) void k_cavlc(Geometry g, const FrameState* __r
     const uint32_t total = __shfl(incl, 31, 32);
     if (lane < kNumRoles) roff[wave][lane] = incl - bits;
     if (lane == kNumRoles) roff[wave][kNumRoles] = total;
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
     const bool fits = total <= kSlotWords * 32u;
     if (!skip && fits) {
         const uint32_t nwords = (total + 31) >> 5;
@@ -2413,34 +2307,11 @@ constexpr int kScanThreads = 256;
 constexpr int kScanRowPer = 2;   // MBs per thread in a row: mb_w <= 512
 constexpr int kScanMaxRows = 512;
 
-template <typename T, typename Op>
-__device__ __forceinline__ T blk_excl_scan(T v, T init, Op op, T* wbuf, T* total) {
-    constexpr int kW = kScanThreads / 64;
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    T incl = v;
-    for (int o = 1; o < 64; o <<= 1) {
-        const T t = __shfl_up(incl, o, 64);
-        if (lane >= o) incl = op(incl, t);
-    }
-    T excl = __shfl_up(incl, 1, 64);
-    if (lane == 0) excl = init;
-    if (lane == 63) wbuf[w] = incl;
-    __syncthreads();
-    T before = init, all = init;
-    for (int k = 0; k < kW; ++k) {
-        if (k < w) before = op(before, wbuf[k]);
-        all = op(all, wbuf[k]);
-    }
-    __syncthreads();
-    *total = all;
-    return op(before, excl);
-}
-
 __device__ __forceinline__ uint32_t blk_excl_sum(uint32_t v, uint32_t* wbuf, uint32_t* total) {
-    return blk_excl_scan<uint32_t>(v, 0u, [](uint32_t a, uint32_t b) { return a + b; }, wbuf, total);
+    return blk_excl_scan<kScanThreads, uint32_t>(v, 0u, [](uint32_t a, uint32_t b) { return a + b; }, wbuf, total);
 }
 __device__ __forceinline__ int blk_excl_max(int v, int init, int* wbuf, int* total) {
-    return blk_excl_scan<int>(v, init, [](int a, int b) { return max(a, b); }, wbuf, total);
+    return blk_excl_scan<kScanThreads, int>(v, init, [](int a, int b) { return max(a, b); }, wbuf, total);
 }
 
 __device__ __forceinline__ SliceParams slice_params(const FrameState* fs, int s, int mb_w) {
@@ -2512,7 +2383,7 @@ __global__ __launch_bounds__(kScanThreads) void k_scan_rows(Geometry g, const Fr
     (void)blk_excl_sum(ncoded, wu, &tc);
     (void)blk_excl_sum(over, wu, &to);
     int firstall;
-    (void)blk_excl_scan<int>(first, 0x7fffffff, [](int x, int y) { return min(x, y); }, wi, &firstall);
+    (void)blk_excl_scan<kScanThreads, int>(first, 0x7fffffff, [](int x, int y) { return min(x, y); }, wi, &firstall);
     if (t == 0)
         row_agg[r] = make_uint4((uint32_t)(lastall >= 0 ? firstall : -1), (uint32_t)lastall,
                                 tc | (to ? 0x80000000u : 0u), tb);
@@ -2760,7 +2631,7 @@ __device__ __forceinline__ uint32_t slot_get(const uint32_t* slot, uint32_t b, i
 
 // One thread per 32-bit output word, four lanes per 16-byte quad: each lane locates its
 // word's first overlapping slice / MB unit (4-ary search over the dense per-rank unit
-// records written by k_scan), assembles the word from the slice header / MB units / slice
+// records written by k_scan_out), assembles the word from the slice header / MB units / slice
 // trailer bits that overlap it, and lane 0 of the quad gathers the four words with lane
 // shuffles and writes them with one 16-byte store straight into pinned host memory.
 // No atomics, no zero-fill pass, short dependent-load chains (latency-bound kernel).
@@ -2814,7 +2685,7 @@ __device__ void pack_body(const Geometry& g, const FrameState* __restrict__ fs, 
         uint32_t acc = 0;
         if (active) {
             const uint32_t W0 = (uint32_t)qbase * 128 + 32 * sub;
-            const int qa = (int)quad_unit[qbase];  // unit holding the quad's first bit (k_scan)
+            const int qa = (int)quad_unit[qbase];  // unit holding the quad's first bit (k_scan_out)
             // last slice starting at or before W0
             int lo = 0, hi = ns - 1;
             while (lo < hi) {
@@ -2884,11 +2755,7 @@ void launch_hpel(const Geometry& g, const DeviceBuffers& b, uint8_t* const plane
                  hipStream_t stream, const FrameState* publish) {
     const int W = g.coded_w + 2 * kHpelPad, H = g.coded_h + 2 * kHpelPad;
     dim3 grid((W + kHpTW - 1) / kHpTW, (H + kHpTH - 1) / kHpTH);
-    StateArg sa{};
-    if (publish) sa.v = *publish;
-    sa.dst = b.fs;
-    sa.publish = publish ? 1 : 0;
-    sa.t_start = b.out_hdr ? &b.out_hdr->t_start : nullptr;
+    const StateArg sa = make_state_arg(b, publish);
     hipLaunchKernelGGL(k_hpel, grid, dim3(256), 0, stream, g, sa, planes[0], planes[1], planes[2], planes[3],
                        hp_pitch);
 }
@@ -2911,11 +2778,7 @@ void launch_mc_luma_test(const Geometry& g, const uint8_t* ref, int x4, int y4, 
 void launch_me(const Geometry& g, const DeviceBuffers& b, const uint8_t* src_y, hipStream_t stream,
                const FrameState* publish, bool side) {
     const int nmb = g.mb_w * g.mb_h;
-    StateArg sa{};
-    if (publish) sa.v = *publish;
-    sa.dst = b.fs;
-    sa.publish = publish ? 1 : 0;
-    sa.t_start = b.out_hdr ? &b.out_hdr->t_start : nullptr;  // H.264: a P picture's first kernel
+    const StateArg sa = make_state_arg(b, publish);  // H.264: a P picture's first kernel
     if (side && publish)
         hipLaunchKernelGGL(k_me_full_val, dim3(nmb), dim3(kMeThreads), 0, stream, g, sa, src_y, b.mb);
     else
@@ -2932,11 +2795,7 @@ void launch_inter(const Geometry& g, const DeviceBuffers& b, const uint8_t* src_
 void launch_p_fused(const Geometry& g, const DeviceBuffers& b, const uint8_t* src_y, const uint8_t* src_uv,
                     hipStream_t stream, const FrameState* publish) {
     const int nmb = g.mb_w * g.mb_h;
-    StateArg sa{};
-    if (publish) sa.v = *publish;
-    sa.dst = b.fs;
-    sa.publish = publish ? 1 : 0;
-    sa.t_start = b.out_hdr ? &b.out_hdr->t_start : nullptr;
+    const StateArg sa = make_state_arg(b, publish);
     hipLaunchKernelGGL(k_p_fused, dim3(nmb), dim3(kMeThreads), 0, stream, g, sa, src_y, src_uv, b.mb, b.coef, b.mb_sse,
                        b.wave_prog);
 }
@@ -2944,12 +2803,8 @@ void launch_p_fused(const Geometry& g, const DeviceBuffers& b, const uint8_t* sr
 static void launch_analyze(const Geometry& g, const DeviceBuffers& b, const uint8_t* src_y, const uint8_t* src_uv,
                            hipStream_t stream, const FrameState* publish, bool first) {
     const int nmb = g.mb_w * g.mb_h;
-    StateArg sa{};
-    if (publish) sa.v = *publish;
-    sa.dst = b.fs;
-    sa.publish = publish ? 1 : 0;
     // the first kernel of an I picture stamps the start; in a P picture k_me_full did
-    sa.t_start = (b.out_hdr && first) ? &b.out_hdr->t_start : nullptr;
+    const StateArg sa = make_state_arg(b, publish, first);
     hipLaunchKernelGGL(k_intra_analyze, dim3((nmb + 3) / 4), dim3(256), 0, stream, g, sa, src_y, src_uv, b.mb,
                        b.wave_prog, b.intra_gain, b.intra_cand);
 }
@@ -2970,7 +2825,7 @@ void launch_intra(const Geometry& g, const DeviceBuffers& b, const uint8_t* src_
     const size_t lds = (size_t)rows * g.coded_w;
     // line buffers above the default dynamic-LDS limit (8K: 61 KB + tiles); per device, once
     ensure_func_attr(reinterpret_cast<const void*>(&k_intra_wave), hipFuncAttributeMaxDynamicSharedMemorySize,
-                     160 * 1024 - (int)(sizeof(IntraWaveTiles) + sizeof(LumaPipeTiles)) * 8 - 32);
+                     160 * 1024 - (int)(sizeof(ChromaWaveTiles) + sizeof(LumaPipeTiles)) * 8 - 32);
     hipLaunchKernelGGL(k_intra_wave, dim3(slices, 2), dim3(64 * rows), lds, stream, g, b.fs, src_y, src_uv, b.mb,
                        b.coef);
     hipLaunchKernelGGL(k_intra_cbp, dim3((g.mb_w * g.mb_h + 255) / 256), dim3(256), 0, stream, g, b.mb);

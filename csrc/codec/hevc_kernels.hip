@@ -29,6 +29,7 @@
 
 #include <stdexcept>
 
+#include "../common/wave.h"
 #include "h264_core.h"
 #include "h264_gpu.h"
 #include "h264_mb.h"
@@ -40,33 +41,6 @@ namespace hevc {
 
 namespace {
 
-// Cross-row exchanges without LDS (CDNA4 v_permlane16/32_swap with both operands = v): the
-// swapped pair holds {v, v ^ 16} (resp. {v, v ^ 32}) in some order on every lane, so their
-// sum / max / or is the xor-16 (xor-32) step of a butterfly -- no ds_bpermute round trip.
-__device__ __forceinline__ void xrow16(uint32_t v, uint32_t& a, uint32_t& b) {
-    const auto r = __builtin_amdgcn_permlane16_swap(v, v, false, false);
-    a = r[0];
-    b = r[1];
-}
-__device__ __forceinline__ void xrow32(uint32_t v, uint32_t& a, uint32_t& b) {
-    const auto r = __builtin_amdgcn_permlane32_swap(v, v, false, false);
-    a = r[0];
-    b = r[1];
-}
-// Wave sum, every lane gets it (called with the whole wave active): quad and row-of-16 sums
-// with DPP (quad_perm [1,0,3,2], [2,3,0,1], row_ror 4, row_ror 8), then the four rows with the
-// two permlane swaps -- all VALU, no LDS latency on the (often serial) reduction chains.
-__device__ __forceinline__ int wsum(int v) {
-    v += __builtin_amdgcn_mov_dpp(v, 0xB1, 0xF, 0xF, false);
-    v += __builtin_amdgcn_mov_dpp(v, 0x4E, 0xF, 0xF, false);
-    v += __builtin_amdgcn_mov_dpp(v, 0x124, 0xF, 0xF, false);
-    v += __builtin_amdgcn_mov_dpp(v, 0x128, 0xF, 0xF, false);
-    uint32_t a, b;
-    xrow16((uint32_t)v, a, b);
-    v = (int)(a + b);
-    xrow32((uint32_t)v, a, b);
-    return (int)(a + b);
-}
 // reductions inside aligned groups of G lanes (G = 8 or 16): every lane gets its group's value
 template <int G>
 __device__ __forceinline__ int gsum(int v) {
@@ -77,37 +51,6 @@ template <int G>
 __device__ __forceinline__ int gmax(int v) {
     for (int o = G / 2; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
     return v;
-}
-// wave max / or: the same DPP + permlane butterfly as wsum
-__device__ __forceinline__ int wmax(int v) {
-    v = max(v, __builtin_amdgcn_mov_dpp(v, 0xB1, 0xF, 0xF, false));
-    v = max(v, __builtin_amdgcn_mov_dpp(v, 0x4E, 0xF, 0xF, false));
-    v = max(v, __builtin_amdgcn_mov_dpp(v, 0x124, 0xF, 0xF, false));
-    v = max(v, __builtin_amdgcn_mov_dpp(v, 0x128, 0xF, 0xF, false));
-    uint32_t a, b;
-    xrow16((uint32_t)v, a, b);
-    v = max((int)a, (int)b);
-    xrow32((uint32_t)v, a, b);
-    return max((int)a, (int)b);
-}
-__device__ __forceinline__ uint32_t wor(uint32_t v) {
-    v |= (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0xB1, 0xF, 0xF, false);
-    v |= (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x4E, 0xF, 0xF, false);
-    v |= (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x124, 0xF, 0xF, false);
-    v |= (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x128, 0xF, 0xF, false);
-    uint32_t a, b;
-    xrow16(v, a, b);
-    xrow32(a | b, a, b);
-    return a | b;
-}
-
-// LDS hand-off between the lanes of ONE wave (its own LDS writes visible to its own later reads;
-// LDS operations of a wave complete in order): no workgroup barrier, so the waves of a workgroup
-// may take different branches around it.
-__device__ __forceinline__ void wave_lds_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 // Stage separator of the TU helpers: wave-local (every wave has its own LDS scratch; the intra
 // wavefront's rows synchronise through progress counters, not workgroup barriers).
@@ -232,9 +175,9 @@ __device__ __forceinline__ TuResult code_tus(TuBuf& t, const Mats& M, int qp, in
         }
     }
     // decimation (wave-uniform decisions per TU), then levels / dequantised values / summaries
-    const bool drop_y = tu_decimate(4, intra, wsum(nzl), wmax(mxl));
-    const bool drop_cb = tu_decimate(3, intra, wsum(comp == 0 ? nzc : 0), wmax(comp == 0 ? mxc : 0));
-    const bool drop_cr = tu_decimate(3, intra, wsum(comp == 1 ? nzc : 0), wmax(comp == 1 ? mxc : 0));
+    const bool drop_y = tu_decimate(4, intra, wave_sum(nzl), wave_max(mxl));
+    const bool drop_cb = tu_decimate(3, intra, wave_sum(comp == 0 ? nzc : 0), wave_max(comp == 0 ? mxc : 0));
+    const bool drop_cr = tu_decimate(3, intra, wave_sum(comp == 1 ? nzc : 0), wave_max(comp == 1 ? mxc : 0));
     const bool drop_c = comp ? drop_cr : drop_cb;
     if (drop_y)
         for (int j = 0; j < 4; ++j) ll[j] = 0;
@@ -247,7 +190,7 @@ __device__ __forceinline__ TuResult code_tus(TuBuf& t, const Mats& M, int qp, in
             int last = -1;
             for (int j = 0; j < 4; ++j)
                 if (ll[j]) last = max(last, scan_index(4, (lane * 4 + j) & 15, (lane * 4 + j) >> 4));
-            last = wmax(last);
+            last = wave_max(last);
             if (last < 0) break;
             int prev = -1, lv = 0;
             for (int j = 0; j < 4; ++j) {
@@ -255,8 +198,8 @@ __device__ __forceinline__ TuResult code_tus(TuBuf& t, const Mats& M, int qp, in
                 if (ll[j] && si < last) prev = max(prev, si);
                 if (si == last) lv = abs(ll[j]);
             }
-            prev = wmax(prev);
-            lv = wmax(lv);
+            prev = wave_max(prev);
+            lv = wave_max(lv);
             if (lv != 1 || last - prev <= kTrimGap) break;
             for (int j = 0; j < 4; ++j)
                 if (scan_index(4, (lane * 4 + j) & 15, (lane * 4 + j) >> 4) == last) ll[j] = 0;
@@ -268,7 +211,7 @@ __device__ __forceinline__ TuResult code_tus(TuBuf& t, const Mats& M, int qp, in
                     const int idx = cl * 2 + j;
                     if (comp == cc && lc[j]) last = max(last, scan_index(3, idx & 7, idx >> 3));
                 }
-                last = wmax(last);
+                last = wave_max(last);
                 if (last < 0) break;
                 int prev = -1, lv = 0;
                 for (int j = 0; j < 2; ++j) {
@@ -276,8 +219,8 @@ __device__ __forceinline__ TuResult code_tus(TuBuf& t, const Mats& M, int qp, in
                     if (comp == cc && lc[j] && si < last) prev = max(prev, si);
                     if (comp == cc && si == last) lv = abs(lc[j]);
                 }
-                prev = wmax(prev);
-                lv = wmax(lv);
+                prev = wave_max(prev);
+                lv = wave_max(lv);
                 if (lv != 1 || last - prev <= kTrimGap) break;
                 for (int j = 0; j < 2; ++j) {
                     const int idx = cl * 2 + j;
@@ -316,20 +259,20 @@ __device__ __forceinline__ TuResult code_tus(TuBuf& t, const Mats& M, int qp, in
             }
         }
     }
-    out.nz[0] = wsum(nzl);
-    out.last[0] = wmax(lastl);
-    out.csbf[0] = wor(csl);
+    out.nz[0] = wave_sum(nzl);
+    out.last[0] = wave_max(lastl);
+    out.csbf[0] = wave_or(csl);
     {
-        const int n_cb = wsum(comp == 0 ? nzc : 0), n_cr = wsum(comp == 1 ? nzc : 0);
+        const int n_cb = wave_sum(comp == 0 ? nzc : 0), n_cr = wave_sum(comp == 1 ? nzc : 0);
         out.nz[1] = n_cb;
         out.nz[2] = n_cr;
-        out.last[1] = wmax(comp == 0 ? lastc : -1);
-        out.last[2] = wmax(comp == 1 ? lastc : -1);
-        out.csbf[1] = wor(comp == 0 ? csc : 0u);
-        out.csbf[2] = wor(comp == 1 ? csc : 0u);
+        out.last[1] = wave_max(comp == 0 ? lastc : -1);
+        out.last[2] = wave_max(comp == 1 ? lastc : -1);
+        out.csbf[1] = wave_or(comp == 0 ? csc : 0u);
+        out.csbf[2] = wave_or(comp == 1 ? csc : 0u);
     }
     {
-        const int bl = wsum(lbits), bcb = wsum(comp == 0 ? cbits : 0), bcr = wsum(comp == 1 ? cbits : 0);
+        const int bl = wave_sum(lbits), bcb = wave_sum(comp == 0 ? cbits : 0), bcr = wave_sum(comp == 1 ? cbits : 0);
         out.bits = (uint32_t)((out.nz[0] ? bl + 4 : 1) + (out.nz[1] ? bcb + 4 : 1) + (out.nz[2] ? bcr + 4 : 1));
         out.bits_y = (uint32_t)(out.nz[0] ? bl + 4 : 1);
     }
@@ -383,11 +326,11 @@ __device__ __forceinline__ TuResult code_tus(TuBuf& t, const Mats& M, int qp, in
             rec_uv[(size_t)yc * pitch_y + 2 * xc + comp] = (uint8_t)v;
         }
     }
-    out.sse[0] = wsum(sy);
-    out.sse[1] = wsum(comp == 0 ? sc : 0);
-    out.sse[2] = wsum(comp == 1 ? sc : 0);
-    out.sse_full = wsum(sf);
-    out.sse_y_full = wsum(syf);
+    out.sse[0] = wave_sum(sy);
+    out.sse[1] = wave_sum(comp == 0 ? sc : 0);
+    out.sse[2] = wave_sum(comp == 1 ? sc : 0);
+    out.sse_full = wave_sum(sf);
+    out.sse_y_full = wave_sum(syf);
     return out;
 }
 
@@ -601,8 +544,8 @@ __device__ __forceinline__ SplitResult split_tus(TuBuf& t, const Mats& M, int qp
     bl = gsum<16>(bl);
     bc = gsum<8>(bc);
     SplitResult out;
-    out.bits = (uint32_t)wsum(((lane & 15) == 0 ? (nzl ? bl + 4 : 1) : 0) + ((lane & 7) == 0 ? (nzc ? bc + 4 : 1) : 0));
-    out.bits_y = (uint32_t)wsum((lane & 15) == 0 ? (nzl ? bl + 4 : 1) : 0);
+    out.bits = (uint32_t)wave_sum(((lane & 15) == 0 ? (nzl ? bl + 4 : 1) : 0) + ((lane & 7) == 0 ? (nzc ? bc + 4 : 1) : 0));
+    out.bits_y = (uint32_t)wave_sum((lane & 15) == 0 ? (nzl ? bl + 4 : 1) : 0);
     wave_lds_sync();
     // ---- inverse stage 1 (columns)
     if (valid) {
@@ -643,11 +586,11 @@ __device__ __forceinline__ SplitResult split_tus(TuBuf& t, const Mats& M, int qp
             rec[o] = (uint8_t)v;
         }
     }
-    out.sse_full = wsum(sf);
-    out.sse_y_full = wsum(syf);
-    out.sse[0] = wsum(sy);
-    out.sse[1] = wsum(comp == 0 ? sc : 0);
-    out.sse[2] = wsum(comp == 1 ? sc : 0);
+    out.sse_full = wave_sum(sf);
+    out.sse_y_full = wave_sum(syf);
+    out.sse[0] = wave_sum(sy);
+    out.sse[1] = wave_sum(comp == 0 ? sc : 0);
+    out.sse[2] = wave_sum(comp == 1 ? sc : 0);
     {  // per luma node: the 16-lane group sums, read from the group's first lane
         const int gs = gsum<16>(syf), gd = gsum<16>(sy);
 #pragma unroll
@@ -901,8 +844,8 @@ __global__ __launch_bounds__(256) void k_hevc_inter(Geometry g, const HevcFrameS
             dcp[comp] = (2 * xc < g.width && 2 * yc < g.height) ? (s - p) * (s - p) : 0;
         }
     }
-    const int tcls = h264::temporal_class((uint32_t)wsum(tsad), mvx == 0 && mvy == 0);  // vector wave-uniform
-    const int qp = h264::mb_qp_for(fs->qp, (uint32_t)wsum(lsad), tcls, fs->aq);  // wave-uniform
+    const int tcls = h264::temporal_class((uint32_t)wave_sum(tsad), mvx == 0 && mvy == 0);  // vector wave-uniform
+    const int qp = h264::mb_qp_for(fs->qp, (uint32_t)wave_sum(lsad), tcls, fs->aq);  // wave-uniform
     const int qpc = chroma_qp(qp, fs->chroma_qp_offset);
     // changing content (aq 3): chroma residual dropped, luma kept only if it pays for its bits
     const bool changing = fs->aq >= 3 && tcls == h264::kTcChanging;
@@ -964,12 +907,12 @@ __global__ __launch_bounds__(256) void k_hevc_inter(Geometry g, const HevcFrameS
     }
     // rate-distortion residual drop of changing content (h264_mb.h drop_luma_for): the luma
     // residual must lower the distortion by more than lambda * (estimated bits)
-    const long long d_pred = wsum(dpf);
+    const long long d_pred = wave_sum(dpf);
     const bool drop = cdrop && valid &&
                       d_pred - (long long)(split ? r2.sse_y_full : r.sse_y_full) <
                           (long long)h264::lambda_sse(qp) * (long long)(split ? r2.bits_y : r.bits_y);  // wave-uniform
-    const int dp_disp = wsum(dpm);
-    const int dcp_u = wsum(dcp[0]), dcp_v = wsum(dcp[1]);  // chroma distortion when its residual is dropped
+    const int dp_disp = wave_sum(dpm);
+    const int dcp_u = wave_sum(dcp[0]), dcp_v = wave_sum(dcp[1]);  // chroma distortion when its residual is dropped
     if (drop) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // after this lane's coded levels / reconstruction
         for (int k = lane; k < 256; k += 64) co[k] = 0;
@@ -1206,7 +1149,7 @@ __global__ __launch_bounds__(256) void k_hevc_intra_modes(Geometry g, const Hevc
             R.TF[k] = (R.T[k + 1] + 2 * R.T[k] + R.T[k - 1] + 2) >> 2;
         }
     }
-    const int sdc = wsum(lane < 16 ? R.L[1 + lane] + R.T[1 + lane] : 0);
+    const int sdc = wave_sum(lane < 16 ? R.L[1 + lane] + R.T[1 + lane] : 0);
     if (lane == 0) R.dc = (sdc + 16) >> 5;
     wave_lds_sync();
     // 4x4 Hadamard SATD of all sixteen 4x4 blocks of the unit on the matrix cores: with the
@@ -1246,7 +1189,7 @@ __global__ __launch_bounds__(256) void k_hevc_intra_modes(Geometry g, const Hevc
         const mf_f4 sm = __builtin_amdgcn_mfma_f32_16x16x16f16(hm, tb, zero, 0, 0, 0);
         const int sad = (int)(__builtin_fabsf(sm[0]) + __builtin_fabsf(sm[1]) + __builtin_fabsf(sm[2]) +
                               __builtin_fabsf(sm[3]));
-        return wsum(sad) + lambda * intra_mode_bits(m, 1, 1);
+        return wave_sum(sad) + lambda * intra_mode_bits(m, 1, 1);
     };
     const int best = intra_mode_search(cost);  // coarse-to-fine: at most 15 of the 35 modes
     int out = best;
@@ -1285,7 +1228,7 @@ __global__ __launch_bounds__(256) void k_hevc_intra_modes(Geometry g, const Hevc
             const mf_f4 sm = __builtin_amdgcn_mfma_f32_16x16x16f16(hm, tb, zero, 0, 0, 0);
             const int sad = (int)(__builtin_fabsf(sm[0]) + __builtin_fabsf(sm[1]) + __builtin_fabsf(sm[2]) +
                                   __builtin_fabsf(sm[3]));
-            return wsum(sad) + lambda * intra_mode_bits(m, 1, 1);
+            return wave_sum(sad) + lambda * intra_mode_bits(m, 1, 1);
         };
         const int best_s = intra_mode_search(cost_split);
         if (intra_split_wins(cost16, cost_split(best_s), lambda)) out = best_s | kIntraSplitFlag;
@@ -1385,10 +1328,10 @@ __device__ SplitIntraResult split_intra_code(TuBuf& t, SplitRefs& S, const Intra
                     }
                 }
                 // DC: luma L[1..8] (i 8..15) + T[1..8] (i 17..24); chroma c: L[1..4] (q 4..7), T[1..4] (q 9..12)
-                dcl = wsum((i >= 8 && i <= 15) || (i >= 17 && i <= 24) ? v : 0);
+                dcl = wave_sum((i >= 8 && i <= 15) || (i >= 17 && i <= 24) ? v : 0);
                 const int qc = i - 33, qq = qc - 17;
-                dcc0 = wsum(i >= 33 && ((qc >= 4 && qc <= 7) || (qc >= 9 && qc <= 12)) ? v : 0);
-                dcc1 = wsum(i >= 50 && ((qq >= 4 && qq <= 7) || (qq >= 9 && qq <= 12)) ? v : 0);
+                dcc0 = wave_sum(i >= 33 && ((qc >= 4 && qc <= 7) || (qc >= 9 && qc <= 12)) ? v : 0);
+                dcc1 = wave_sum(i >= 50 && ((qq >= 4 && qq <= 7) || (qq >= 9 && qq <= 12)) ? v : 0);
             }
         }
         dcl = (dcl + 8) >> 4;
@@ -1450,9 +1393,9 @@ __device__ SplitIntraResult split_intra_code(TuBuf& t, SplitRefs& S, const Intra
         wave_lds_sync();
     }
     SplitIntraResult out;
-    out.sse[0] = wsum(sse_y);
-    out.sse[1] = wsum(comp == 0 && cl ? sse_c : 0);
-    out.sse[2] = wsum(comp == 1 && cl ? sse_c : 0);
+    out.sse[0] = wave_sum(sse_y);
+    out.sse[1] = wave_sum(comp == 0 && cl ? sse_c : 0);
+    out.sse[2] = wave_sum(comp == 1 && cl ? sse_c : 0);
     // cu_bits_est (split, no 4x4 luma): per TU 4 + 2 floor(log2 |l|) per level, + 4 if coded, else 1
     uint32_t bits = 0;
 #pragma unroll
@@ -1460,7 +1403,7 @@ __device__ SplitIntraResult split_intra_code(TuBuf& t, SplitRefs& S, const Intra
         const int l = lv[64 * j + lane], a = l < 0 ? -l : l;
         const int b = a ? 4 + 2 * (31 - __builtin_clz((uint32_t)a)) : 0;
         if (j < 4) {
-            const int sum = wsum(b);
+            const int sum = wave_sum(b);
             bits += (uint32_t)(__ballot(a != 0) ? sum + 4 : 1);
         } else {  // four 4x4 chroma TUs of 16 levels
             const int sum = gsum<16>(b);
@@ -1626,7 +1569,7 @@ __global__ __launch_bounds__(64 * kMaxSliceRows) void k_hevc_intra(Geometry g, c
             const int sl = lane < 16 ? R.L[1 + lane] + R.T[1 + lane] : 0;
             const int c0 = (lane >= 16 && lane < 24) ? R.Lc[0][lane - 15] + R.Tc[0][lane - 15] : 0;
             const int c1 = (lane >= 24 && lane < 32) ? R.Lc[1][lane - 23] + R.Tc[1][lane - 23] : 0;
-            const int dcl = (wsum(sl) + 16) >> 5, dc0 = (wsum(c0) + 8) >> 4, dc1 = (wsum(c1) + 8) >> 4;
+            const int dcl = (wave_sum(sl) + 16) >> 5, dc0 = (wave_sum(c0) + 8) >> 4, dc1 = (wave_sum(c1) + 8) >> 4;
             wave_lds_sync();
             const int r = lane >> 2, cb = (lane & 3) * 4;
             for (int j = 0; j < 4; ++j) {
@@ -1688,33 +1631,6 @@ __global__ __launch_bounds__(64 * kMaxSliceRows) void k_hevc_intra(Geometry g, c
 // floor(prefix * S / total) is tracked against the next slice's threshold ceil(s * total / S), so
 // a 64-bit division happens per slice start rather than per CU (that division loop cost ~60 us at
 // 4K).  Starts are compacted by a second prefix sum.
-__device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t* wtot, uint32_t* total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = (int)blockDim.x >> 6;
-    uint32_t incl = v;
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t t = __shfl_up(incl, o, 64);
-        if (lane >= o) incl += t;
-    }
-    if (lane == 63) wtot[wave] = incl;
-    __syncthreads();
-    uint32_t before = 0, all = 0;
-    for (int w = 0; w < nw; ++w) {
-        before += w < wave ? wtot[w] : 0u;
-        all += wtot[w];
-    }
-    __syncthreads();
-    *total = all;
-    return before + incl - v;
-}
-
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v) {
-    const int lane = threadIdx.x & 63;
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t t = __shfl_up(v, o, 64);
-        if (lane >= o) v += t;
-    }
-    return v;
-}
 // Scans over per-CU arrays run in tiles of 1024 threads x 4 consecutive CUs (arrays padded with
 // zeros to a whole tile: HevcDeviceBuffers).
 constexpr int kScanTile = 4096;
@@ -2448,14 +2364,6 @@ __device__ __forceinline__ int sao_reduce16(int* v, int lane) {
     return t;
 }
 
-// Each wave works on its own CTB: the phases only need the wave's own LDS writes visible
-// (LDS operations of a wave complete in order), not a workgroup barrier.
-__device__ __forceinline__ void sao_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 __global__ __launch_bounds__(256) void k_hevc_sao(Geometry g, const HevcFrameState* __restrict__ fs,
                                                    const uint8_t* __restrict__ src_y, const uint8_t* __restrict__ src_uv,
                                                    const CuInfo* __restrict__ cus, uint32_t* __restrict__ prm) {
@@ -2468,7 +2376,6 @@ __global__ __launch_bounds__(256) void k_hevc_sao(Geometry g, const HevcFrameSta
     const int bid = blockIdx.x, cw = ctb_cols(g.mb_w);
     const int ux = 2 * (bid % cw) + (wave & 1), uy = 2 * (bid / cw) + (wave >> 1);
     const bool valid = ux < g.mb_w && uy < g.mb_h;
-    const int i = valid ? uy * g.mb_w + ux : 0;
     const int x0 = valid ? ux * kCtb : 0, y0 = valid ? uy * kCtb : 0;
     SaoWave& S = sw[wave];
     const uint8_t* ry = fs->rec_y;
@@ -2476,7 +2383,7 @@ __global__ __launch_bounds__(256) void k_hevc_sao(Geometry g, const HevcFrameSta
     const int W = g.coded_w, H = g.coded_h, Wc = W / 2, Hc = H / 2;
     for (int k = lane; k < 96; k += 64) (&S.bo[0][0])[k] = 0;
     if (lane < 48) (&S.eo[0][0])[lane] = 0;
-    sao_wave_sync();
+    wave_lds_sync();
     const int r = lane >> 2, c0 = (lane & 3) * 4;
     const int xc = x0 / 2 + (lane & 7), yc = y0 / 2 + (lane >> 3);
     // no residual anywhere in the CTB of a P picture (sao_keep_ctb): SAO off, the samples are only
@@ -2557,7 +2464,7 @@ __global__ __launch_bounds__(256) void k_hevc_sao(Geometry g, const HevcFrameSta
             S.ob[comp][b] = o;
         }
     }
-    sao_wave_sync();
+    wave_lds_sync();
     // ---- per component: best band window (lexicographic min of (cost, position) over 32 lanes)
     //      and the edge-class sums
     if (valid && !keep) {
@@ -2588,7 +2495,7 @@ __global__ __launch_bounds__(256) void k_hevc_sao(Geometry g, const HevcFrameSta
             for (int q = 0; q < 4; ++q) c.eo_off[k][q] = S.oeo[comp][4 * k + q];
         }
     }
-    sao_wave_sync();
+    wave_lds_sync();
     if (valid && lane == 0) {
         uint32_t w[3] = {0u, 0u, 0u};
         if (!keep) sao_combine(S.ch[0], S.ch[1], S.ch[2], lam16, w);
@@ -2597,7 +2504,7 @@ __global__ __launch_bounds__(256) void k_hevc_sao(Geometry g, const HevcFrameSta
         S.w[2] = w[2];
         if (wave == 0) *reinterpret_cast<uint4*>(prm + 4 * (size_t)bid) = make_uint4(w[0], w[1], w[2], 0u);
     }
-    sao_wave_sync();
+    wave_lds_sync();
     // ---- apply into the output picture; distortion over the display area
     int ey = 0, eu = 0, ev = 0;
     if (valid) {
@@ -2623,9 +2530,9 @@ __global__ __launch_bounds__(256) void k_hevc_sao(Geometry g, const HevcFrameSta
         eu = disp ? du * du : 0;
         ev = disp ? dv * dv : 0;
     }
-    ey = wsum(ey);
-    eu = wsum(eu);
-    ev = wsum(ev);
+    ey = wave_sum(ey);
+    eu = wave_sum(eu);
+    ev = wave_sum(ev);
     if (lane == 0) {
         // 4th channel: luma of units outside the quality-report mask
         const int cx = ux, cy = uy;

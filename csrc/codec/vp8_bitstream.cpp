@@ -183,7 +183,7 @@ void code_tokens(const FrameDesc& f, const Vp8Mb* mbs, const std::function<const
             }
             for (int c = 0; c < 2; ++c)
                 for (int b = 0; b < 4; ++b) {  // chroma (type 2)
-                    const int blk = 16 + 4 * c + b, bx = b & 1, by = b >> 1;
+                    const int blk = 16 + 4 * c + b, by = b >> 1;
                     const int above = by > 0 ? nzb(m, blk - 2) : (up ? nzb(*up, blk + 2) : 0);
                     put_block(e, lv + blk * 16, 0, 2, above + left[4 + 2 * c + by]);
                     left[4 + 2 * c + by] = nzb(m, blk);

@@ -23,6 +23,7 @@
 #include <cstdlib>
 
 #include "../common/hip_check.h"
+#include "../common/wave.h"
 #include "h264_core.h"
 #include "h264_gpu.h"
 #include "h264_mb.h"
@@ -36,20 +37,6 @@ namespace {
 typedef __attribute__((address_space(1))) uint64_t gu64;
 typedef __attribute__((address_space(1))) uint32_t gu32;
 constexpr unsigned kSpinLimit = 1u << 22;
-
-// Wave sum, every lane gets it (whole wave active): DPP within rows of 16 (quad_perm
-// [1,0,3,2], [2,3,0,1], row_ror 4, row_ror 8), then v_permlane16/32_swap with both operands = v,
-// whose pair holds {v, v ^ 16} / {v, v ^ 32} -- no ds_bpermute round trips.
-__device__ __forceinline__ int wsum(int v) {
-    v += __builtin_amdgcn_mov_dpp(v, 0xB1, 0xF, 0xF, false);
-    v += __builtin_amdgcn_mov_dpp(v, 0x4E, 0xF, 0xF, false);
-    v += __builtin_amdgcn_mov_dpp(v, 0x124, 0xF, 0xF, false);
-    v += __builtin_amdgcn_mov_dpp(v, 0x128, 0xF, 0xF, false);
-    const auto r16 = __builtin_amdgcn_permlane16_swap((uint32_t)v, (uint32_t)v, false, false);
-    const uint32_t u = r16[0] + r16[1];
-    const auto r32 = __builtin_amdgcn_permlane32_swap(u, u, false, false);
-    return (int)(r32[0] + r32[1]);
-}
 
 // dead-zone quantiser of vp8_core.h quantize(): (3|c| + q) / (3q) as a multiply-high
 __device__ __forceinline__ int qz(int c, int q, uint32_t m) {
@@ -186,8 +173,8 @@ __device__ uint32_t code_mb(MbLds& s, const Vp8FrameState& F, int16_t* __restric
     }
     bool drop = false;
     if (drop_lambda >= 0) {  // wave-uniform
-        const uint32_t lsad = (uint32_t)wsum(st_lsad), bits = (uint32_t)wsum(st_bits);
-        drop = vp8_drop_residual(lsad, (long long)wsum(st_dp), (long long)wsum(st_dc), bits, drop_lambda);
+        const uint32_t lsad = (uint32_t)wave_sum(st_lsad), bits = (uint32_t)wave_sum(st_bits);
+        drop = vp8_drop_residual(lsad, (long long)wave_sum(st_dp), (long long)wave_sum(st_dc), bits, drop_lambda);
     }
     if (drop) {
         nz = false;
@@ -269,9 +256,9 @@ __device__ __forceinline__ void store_rec(const MbLds& s, const h264::Geometry& 
     const bool vis = 2 * (x0 / 2 + cx) < g.width && 2 * (y0 / 2 + cy) < g.height;
     const int eu = (int)s.su[cy * 8 + cx] - (int)s.ru[cy * 8 + cx];
     const int ev = (int)s.sv[cy * 8 + cx] - (int)s.rv[cy * 8 + cx];
-    sse[0] = (uint32_t)wsum(ey);
-    sse[1] = (uint32_t)wsum(vis ? eu * eu : 0);
-    sse[2] = (uint32_t)wsum(vis ? ev * ev : 0);
+    sse[0] = (uint32_t)wave_sum(ey);
+    sse[1] = (uint32_t)wave_sum(vis ? eu * eu : 0);
+    sse[2] = (uint32_t)wave_sum(vis ? ev * ev : 0);
 }
 
 // store_rec without the stores: the reconstruction's words (luma one per lane, chroma one per lane
@@ -293,9 +280,9 @@ __device__ __forceinline__ void rec_words(const MbLds& s, const h264::Geometry& 
     const bool vis = 2 * (x0 / 2 + cx) < g.width && 2 * (y0 / 2 + cy) < g.height;
     const int eu = (int)s.su[cy * 8 + cx] - (int)s.ru[cy * 8 + cx];
     const int ev = (int)s.sv[cy * 8 + cx] - (int)s.rv[cy * 8 + cx];
-    sse[0] = (uint32_t)wsum(ey);
-    sse[1] = (uint32_t)wsum(vis ? eu * eu : 0);
-    sse[2] = (uint32_t)wsum(vis ? ev * ev : 0);
+    sse[0] = (uint32_t)wave_sum(ey);
+    sse[1] = (uint32_t)wave_sum(vis ? eu * eu : 0);
+    sse[2] = (uint32_t)wave_sum(vis ? ev * ev : 0);
 }
 
 __device__ __forceinline__ void store_record(Vp8Mb* __restrict__ rec, int mvx, int mvy, int ymode, int uvmode,
@@ -406,7 +393,7 @@ __global__ __launch_bounds__(64) void k_vp8_inter(h264::Geometry g, const Vp8Sta
             tsad += abs((int)((sw >> (8 * j)) & 0xff) -
                         h264::ref_px(F.prev_src, g.pitch, g.coded_w, g.coded_h, x0 + c4 + j + ix, y0 + r + iy));
         *reinterpret_cast<uint32_t*>(F.save_src + (size_t)(y0 + r) * g.pitch + x0 + c4) = sw;
-        seg = seg_of_tclass(h264::temporal_class((uint32_t)wsum(tsad), mvx == 0 && mvy == 0));  // wave-uniform
+        seg = seg_of_tclass(h264::temporal_class((uint32_t)wave_sum(tsad), mvx == 0 && mvy == 0));  // wave-uniform
     }
     const int cvx = chroma_mv(mvx), cvy = chroma_mv(mvy);
     {
@@ -434,7 +421,7 @@ __global__ __launch_bounds__(64) void k_vp8_inter(h264::Geometry g, const Vp8Sta
 #pragma unroll
         for (int j = 0; j < 4; ++j) psad += abs((int)s.src[r * 16 + c4 + j] - (int)s.pred[r * 16 + c4 + j]);
     }
-    psad = wsum(psad);
+    psad = wave_sum(psad);
     const uint32_t nz = code_mb(s, F, lv + (size_t)mbi * kCoefPerMb, lane, F.drop_lambda, seg);
     uint32_t sse[3];
     store_rec(s, g, F, x0, y0, lane, sse);
@@ -480,20 +467,13 @@ __device__ __forceinline__ int dc_value(int sum, int cnt, int log2n) {
 struct BpLds {
     int X[16];
 };
-__device__ __forceinline__ void wave_lds_sync() {  // this wave's LDS writes before its later reads
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 // raster position -> scan index (the inverse of kZigzag), 4 bits each
 constexpr uint64_t kInvZigzagPacked = 0xFEA9DB83C7426510ull;
 // v[i] of i in 0..3 as bitwise blends (no select the compiler could turn into a branch)
 __device__ __forceinline__ int pick4(int i, int a, int b, int c, int d) {
     return (a & -(int)(i == 0)) | (b & -(int)(i == 1)) | (c & -(int)(i == 2)) | (d & -(int)(i == 3));
 }
-// quad broadcast of lane 4 (l / 4) + k; rotation within a row of 16: lane i <- lane (i - n) & 15
-template <int k>
-__device__ __forceinline__ int qbc(int v) { return __builtin_amdgcn_mov_dpp(v, k * 0x55, 0xF, 0xF, false); }
+// rotation within a row of 16: lane i <- lane (i - n) & 15
 template <int n>
 __device__ __forceinline__ int rror(int v) { return __builtin_amdgcn_mov_dpp(v, 0x120 + n, 0xF, 0xF, false); }
 // the values of column c (rows 0..3) for lane 4 r + c of every 16-lane row: rows r, r-1, r-2, r-3
@@ -645,7 +625,7 @@ __global__ __launch_bounds__(256) void k_vp8_bpred_plan(h264::Geometry g, const 
     const int r16 = lane >> 2, c4 = (lane & 3) * 4;
     const int corner = !at ? 127 : (!al ? 129 : src(x0 - 1, y0 - 1));
     const int lft = al ? src(x0 - 1, y0 + r16) : 129;
-    const int dcy = dc_value(wsum((lane < 16 && at ? src(x0 + lane, y0 - 1) : 0) + (lane >= 16 && lane < 32 && al ? src(x0 - 1, y0 + lane - 16) : 0)),
+    const int dcy = dc_value(wave_sum((lane < 16 && at ? src(x0 + lane, y0 - 1) : 0) + (lane >= 16 && lane < 32 && al ? src(x0 - 1, y0 + lane - 16) : 0)),
                              (at ? 1 : 0) + (al ? 1 : 0), 3);
     uint32_t cost16 = ~0u;
     {
@@ -658,7 +638,7 @@ __global__ __launch_bounds__(256) void k_vp8_bpred_plan(h264::Geometry g, const 
         }
 #pragma unroll
         for (int m = 0; m < 4; ++m) {
-            const uint32_t cst = 256u * (uint32_t)wsum(sad[m]) + (uint32_t)(lam * kf_ymode_cost256(m));
+            const uint32_t cst = 256u * (uint32_t)wave_sum(sad[m]) + (uint32_t)(lam * kf_ymode_cost256(m));
             cost16 = cst < cost16 ? cst : cost16;
         }
     }
@@ -679,9 +659,9 @@ __global__ __launch_bounds__(256) void k_vp8_bpred_plan(h264::Geometry g, const 
             bm = m;
         }
     }
-    const uint32_t costb = (uint32_t)(lam * kf_ymode_cost256(kBPred)) + (uint32_t)wsum(rr == 0 ? (int)best : 0);
-    const uint32_t lo = (uint32_t)wsum(rr == 0 && b < 8 ? (int)((uint32_t)bm << (4 * b)) : 0);
-    const uint32_t hi = (uint32_t)wsum(rr == 0 && b >= 8 ? (int)((uint32_t)bm << (4 * (b - 8))) : 0);
+    const uint32_t costb = (uint32_t)(lam * kf_ymode_cost256(kBPred)) + (uint32_t)wave_sum(rr == 0 ? (int)best : 0);
+    const uint32_t lo = (uint32_t)wave_sum(rr == 0 && b < 8 ? (int)((uint32_t)bm << (4 * b)) : 0);
+    const uint32_t hi = (uint32_t)wave_sum(rr == 0 && b >= 8 ? (int)((uint32_t)bm << (4 * (b - 8))) : 0);
     if (lane == 0) {
         Vp8Mb& m = mbs[mbi];
         m.mvx = (int16_t)(uint16_t)(lo & 0xffffu);
@@ -812,11 +792,11 @@ __global__ __launch_bounds__(64) void k_vp8_key(h264::Geometry g, const Vp8State
         __syncthreads();
         // ---- mode decisions: SAD of the four 16x16 modes (4 samples per lane), the four chroma modes
         const int nav = top ? 0 : 1, nlf = left ? 1 : 0;
-        const int dcy = dc_value(wsum((lane < 16 && !top ? E.ay[lane] : 0) + (lane >= 16 && lane < 32 && left ? E.ly[lane - 16] : 0)),
+        const int dcy = dc_value(wave_sum((lane < 16 && !top ? E.ay[lane] : 0) + (lane >= 16 && lane < 32 && left ? E.ly[lane - 16] : 0)),
                                  nav + nlf, 3);
-        const int dcu = dc_value(wsum((lane < 8 && !top ? E.au[lane] : 0) + (lane >= 8 && lane < 16 && left ? E.lu[lane - 8] : 0)),
+        const int dcu = dc_value(wave_sum((lane < 8 && !top ? E.au[lane] : 0) + (lane >= 8 && lane < 16 && left ? E.lu[lane - 8] : 0)),
                                  nav + nlf, 2);
-        const int dcv = dc_value(wsum((lane < 8 && !top ? E.av[lane] : 0) + (lane >= 8 && lane < 16 && left ? E.lvv[lane - 8] : 0)),
+        const int dcv = dc_value(wave_sum((lane < 8 && !top ? E.av[lane] : 0) + (lane >= 8 && lane < 16 && left ? E.lvv[lane - 8] : 0)),
                                  nav + nlf, 2);
         const int r = lane >> 2, c4 = (lane & 3) * 4;
         int ymode = 0, uvmode = 0;
@@ -831,7 +811,7 @@ __global__ __launch_bounds__(64) void k_vp8_key(h264::Geometry g, const Vp8State
             }
 #pragma unroll
             for (int m = 0; m < 4; ++m) {
-                const uint32_t t = (uint32_t)wsum(sad[m]);
+                const uint32_t t = (uint32_t)wave_sum(sad[m]);
                 if (t < best16) {
                     best16 = t;
                     ymode = m;
@@ -849,7 +829,7 @@ __global__ __launch_bounds__(64) void k_vp8_key(h264::Geometry g, const Vp8State
             uint32_t best = ~0u;
 #pragma unroll
             for (int m = 0; m < 4; ++m) {
-                const uint32_t t = (uint32_t)wsum(sad[m]);
+                const uint32_t t = (uint32_t)wave_sum(sad[m]);
                 if (t < best) {
                     best = t;
                     uvmode = m;
@@ -934,7 +914,7 @@ __device__ __forceinline__ void rec_edges(KeyEdges& E, const h264::Geometry& g, 
 // 16x16 luma mode of least SAD against the staged source (ties: the lower mode), its SAD
 __device__ __forceinline__ int best_luma16(const MbLds& s, const KeyEdges& E, bool top, bool left, int lane,
                                            uint32_t& best) {
-    const int dcy = dc_value(wsum((lane < 16 && !top ? E.ay[lane] : 0) + (lane >= 16 && lane < 32 && left ? E.ly[lane - 16] : 0)),
+    const int dcy = dc_value(wave_sum((lane < 16 && !top ? E.ay[lane] : 0) + (lane >= 16 && lane < 32 && left ? E.ly[lane - 16] : 0)),
                              (top ? 0 : 1) + (left ? 1 : 0), 3);
     const int r = lane >> 2, c4 = (lane & 3) * 4;
     int sad[4] = {0, 0, 0, 0};
@@ -948,7 +928,7 @@ __device__ __forceinline__ int best_luma16(const MbLds& s, const KeyEdges& E, bo
     best = ~0u;
 #pragma unroll
     for (int m = 0; m < 4; ++m) {
-        const uint32_t t = (uint32_t)wsum(sad[m]);
+        const uint32_t t = (uint32_t)wave_sum(sad[m]);
         if (t < best) {
             best = t;
             mode = m;
@@ -1019,11 +999,11 @@ __global__ __launch_bounds__(64) void k_vp8_intra_code(h264::Geometry g, const V
     const bool top = mby == 0, left = mbx > 0;
     const int ymode = ic & 3;
     const int nav = top ? 0 : 1, nlf = left ? 1 : 0;
-    const int dcy = dc_value(wsum((lane < 16 && !top ? E.ay[lane] : 0) + (lane >= 16 && lane < 32 && left ? E.ly[lane - 16] : 0)),
+    const int dcy = dc_value(wave_sum((lane < 16 && !top ? E.ay[lane] : 0) + (lane >= 16 && lane < 32 && left ? E.ly[lane - 16] : 0)),
                              nav + nlf, 3);
-    const int dcu = dc_value(wsum((lane < 8 && !top ? E.au[lane] : 0) + (lane >= 8 && lane < 16 && left ? E.lu[lane - 8] : 0)),
+    const int dcu = dc_value(wave_sum((lane < 8 && !top ? E.au[lane] : 0) + (lane >= 8 && lane < 16 && left ? E.lu[lane - 8] : 0)),
                              nav + nlf, 2);
-    const int dcv = dc_value(wsum((lane < 8 && !top ? E.av[lane] : 0) + (lane >= 8 && lane < 16 && left ? E.lvv[lane - 8] : 0)),
+    const int dcv = dc_value(wave_sum((lane < 8 && !top ? E.av[lane] : 0) + (lane >= 8 && lane < 16 && left ? E.lvv[lane - 8] : 0)),
                              nav + nlf, 2);
     const int r = lane >> 2, c4 = (lane & 3) * 4, cx = lane & 7, cy = lane >> 3;
     int uvmode = 0;
@@ -1036,7 +1016,7 @@ __global__ __launch_bounds__(64) void k_vp8_intra_code(h264::Geometry g, const V
         uint32_t best = ~0u;
 #pragma unroll
         for (int m = 0; m < 4; ++m) {
-            const uint32_t t = (uint32_t)wsum(sad[m]);
+            const uint32_t t = (uint32_t)wave_sum(sad[m]);
             if (t < best) {
                 best = t;
                 uvmode = m;
@@ -1418,7 +1398,7 @@ __global__ __launch_bounds__(256) void k_vp8_lf_sse(h264::Geometry g, const Vp8S
     }
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-        const uint32_t w = (uint32_t)wsum((int)e[c]);
+        const uint32_t w = (uint32_t)wave_sum((int)e[c]);
         if (lane == 0) part[c][wave] = w;
     }
     __syncthreads();
@@ -1480,9 +1460,7 @@ __global__ __launch_bounds__(256) void k_vp8_gather(h264::Geometry g, const Vp8M
             bmap[wave][k] = (uint16_t)((i << 5) | bb);
         }
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
     // two uint4 per block, spread over the lanes: many copies in flight per wave
     const uint4* __restrict__ src = reinterpret_cast<const uint4*>(lv + (size_t)base * kCoefPerMb);
     uint4* __restrict__ dst = reinterpret_cast<uint4*>(lv_host + (row_blk + off) * 16);

@@ -690,8 +690,6 @@ __device__ __forceinline__ mf_h8 mf_chan(const uint4& a, const uint4& b, uint32_
     return __builtin_bit_cast(mf_h8, r);
 }
 
-__device__ __forceinline__ int clamp255(float v) { return min(max((int)__builtin_rintf(v), 0), 255); }
-
 // Stage rows [r0, r0 + 32) of the footprint (clipped to nr) into `buf` with LDS-DMA, one
 // footprint row per wave instruction (rows wave, wave + 2, ...: 16 instructions per wave for a
 // full block): lane q < nq copies input pixels xlo + 4q .. +3 (its clamped byte offset `loff`)
@@ -854,7 +852,7 @@ __global__ __launch_bounds__(128) void k_scale_mfma(const uint8_t* __restrict__ 
     MF_STAMP(1, __builtin_amdgcn_s_memtime());
     // LDS: two 32-row footprint buffers [32][lds_cols] BGRx (see mf_main)
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int tid = threadIdx.x, lane = tid & 63, h = lane >> 5, l32 = lane & 31;
+    const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     // XCD-aware tile order: dispatch round-robins workgroups over the 8 XCDs (each with its own
     // L2), so the linear id is remapped to give every XCD a contiguous band of tiles -- the
@@ -1108,7 +1106,7 @@ __global__ __launch_bounds__(128) void k_scale_strip(const uint8_t* __restrict__
     // LDS: the ring of 32-row footprint blocks [32][lds_cols] BGRx, then the strip's vertical
     // weight fragments [tile][kMfRb][2][64 lanes]
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int tid = threadIdx.x, lane = tid & 63, h = lane >> 5, l32 = lane & 31;
+    const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     int sx, sy;
     {  // XCD-aware order: every XCD a contiguous band of strips (neighbouring footprints share its L2)

@@ -308,7 +308,7 @@ def test_session_masked_psnr_from_encoder(gpu, intra_in_p):
 
 
 def test_session_reports_psnr_of_reconstruction(gpu):
-    """Encoder-side SSE (k_inter_encode / k_intra_rows -> k_scan) equals the PSNR of the
+    """Encoder-side SSE (k_inter_encode / k_intra_wave -> k_scan_rows / k_scan_out) equals the PSNR of the
     independently decoded picture against the source, over the display area only."""
     cfg = gpu.SessionConfig()
     cfg.width, cfg.height, cfg.fps = 200, 120, 60  # coded 208x128: padding must be excluded
