@@ -2,8 +2,8 @@
 //
 // Decomposition (gfx950: 256 CUs, wave64):
 //  * k_me_full      one 256-thread workgroup per macroblock; the search window is staged
-//                   in LDS and every lane scores (2R+1)^2/256 integer candidates with
-//                   v_sad_u8 on byte-aligned dwords (v_alignbyte), then optional
+//                   in LDS and every lane scores (2R+1)^2/256 integer candidates, four
+//                   horizontally adjacent ones per v_qsad_pk_u16_u8, then optional
 //                   quarter-pel refinement; block-wide argmin via shuffles + LDS.
 //  * k_inter_encode one wave per macroblock (4 per workgroup): motion compensation
 //                   (6-tap qpel / bilinear chroma), 4x4 integer transform, quantisation,
@@ -211,6 +211,11 @@ constexpr int kWinRows = 16 + 2 * kMaxRange + 7;
 constexpr int kWinWords = kWinRows * kWinStride / 4;
 
 constexpr int kMeThreads = 256, kMeWaves = kMeThreads / 64;
+// v_qsad_pk_u16_u8: the SADs of `src` against bytes 0..3, 1..4, 2..5 and 3..6 of the 64-bit window
+// hi:lo, each added to its 16-bit field of acc -- four horizontally adjacent candidates at once.
+__device__ __forceinline__ uint64_t qsad4(uint32_t hi, uint32_t lo, uint32_t src, uint64_t acc) {
+    return __builtin_amdgcn_qsad_pk_u16_u8(((uint64_t)hi << 32) | lo, src, acc);
+}
 // F / H / V / J footprints (18x18 each, the layout qpel_lds reads) around `n` (1 or 2) integer
 // matches, computed from the staged window with k_hpel's arithmetic: unclipped horizontal six-tap
 // intermediates b1, H = (b1 + 16) >> 5, V the same from the sample column, J = (six taps over
@@ -338,7 +343,8 @@ __device__ __forceinline__ MbInfo me_full_body(const Geometry& g, const MeState&
 
     // Each thread scores four horizontally adjacent candidates per step: their 16x16 blocks
     // share one dword-aligned 20-byte row span of the window, so every row costs 5 LDS reads
-    // (instead of 5 per candidate), 12 v_alignbyte and 16 v_sad_u8.
+    // (instead of 5 per candidate) and 4 v_qsad_pk_u16_u8 (qsad4; 12 v_alignbyte + 16 v_sad_u8
+    // before: k_p_fused 61.8 -> 55.3 us at 1080p, k_me_full 87.1 -> 78.9 us at 4K, profiles/p_quad).
     const int side = 2 * R + 1, gw = (side + 3) >> 2, ngroups = side * gw;
     unsigned long long best = ~0ull;
     const bool coarse = st.me_coarse != 0;
@@ -369,32 +375,25 @@ __device__ __forceinline__ MbInfo me_full_body(const Geometry& g, const MeState&
         const int nsh = coarse ? 2 : 4, ntp = coarse ? (R + 1) * gw : ngroups;
         for (int q = tid; q < ntp; q += kMeThreads) {
             const int dyr = coarse ? 2 * (q / gw) : q / gw, g = q % gw;
-            uint32_t acc[4][4];  // [shift index][quadrant]
-#pragma unroll
-            for (int i = 0; i < 4; ++i) acc[i][0] = acc[i][1] = acc[i][2] = acc[i][3] = 0;
+            // one packed accumulator per quadrant: the four shifted SADs of the dword group as 16-bit
+            // sums (a quadrant's is <= 8 * 8 * 255), a v_qsad_pk_u16_u8 per source dword and row
+            uint64_t acc[4] = {0, 0, 0, 0};
 #pragma unroll 2
             for (int r = 0; r < 16; ++r) {
                 const int a = (dyr + r) * kWs4 + g, hq = r < 8 ? 0 : 2;
                 const uint32_t w0 = win32[a], w1 = win32[a + 1], w2 = win32[a + 2], w3 = win32[a + 3], w4 = win32[a + 4];
                 const uint32_t s0 = srcw[r * 4 + 0], s1 = srcw[r * 4 + 1], s2 = srcw[r * 4 + 2], s3 = srcw[r * 4 + 3];
-#pragma unroll
-                for (int si = 0; si < 4; ++si) {
-                    if (si >= nsh) break;
-                    const int sh = coarse ? 2 * si : si;
-                    const uint32_t a0 = sh ? __builtin_amdgcn_alignbyte(w1, w0, sh) : w0;
-                    const uint32_t a1 = sh ? __builtin_amdgcn_alignbyte(w2, w1, sh) : w1;
-                    const uint32_t a2 = sh ? __builtin_amdgcn_alignbyte(w3, w2, sh) : w2;
-                    const uint32_t a3 = sh ? __builtin_amdgcn_alignbyte(w4, w3, sh) : w3;
-                    uint32_t lft = hq ? acc[si][2] : acc[si][0], rgt = hq ? acc[si][3] : acc[si][1];
-                    lft = __builtin_amdgcn_sad_u8(a1, s1, __builtin_amdgcn_sad_u8(a0, s0, lft));
-                    rgt = __builtin_amdgcn_sad_u8(a3, s3, __builtin_amdgcn_sad_u8(a2, s2, rgt));
-                    if (hq) {
-                        acc[si][2] = lft;
-                        acc[si][3] = rgt;
-                    } else {
-                        acc[si][0] = lft;
-                        acc[si][1] = rgt;
-                    }
+                uint64_t lft = hq ? acc[2] : acc[0], rgt = hq ? acc[3] : acc[1];
+                lft = qsad4(w1, w0, s0, lft);
+                lft = qsad4(w2, w1, s1, lft);
+                rgt = qsad4(w3, w2, s2, rgt);
+                rgt = qsad4(w4, w3, s3, rgt);
+                if (hq) {
+                    acc[2] = lft;
+                    acc[3] = rgt;
+                } else {
+                    acc[0] = lft;
+                    acc[1] = rgt;
                 }
             }
 #pragma unroll
@@ -402,27 +401,27 @@ __device__ __forceinline__ MbInfo me_full_body(const Geometry& g, const MeState&
                 if (si >= nsh) break;
                 const int dxr = 4 * g + (coarse ? 2 * si : si);
                 if (dxr >= side) break;
-                visit_quads(acc[si], dxr, dyr);
+                const int sh = 16 * (coarse ? 2 * si : si);
+                const uint32_t qd[4] = {(uint32_t)(acc[0] >> sh) & 0xffffu, (uint32_t)(acc[1] >> sh) & 0xffffu,
+                                        (uint32_t)(acc[2] >> sh) & 0xffffu, (uint32_t)(acc[3] >> sh) & 0xffffu};
+                visit_quads(qd, dxr, dyr);
             }
         }
     }
     for (int q = tid; q < ntask; q += kMeThreads) {
         const int dyr = 2 * (q / gw), g = q % gw;
-        uint32_t s0a = 0, s2a = 0;
+        uint64_t acc = 0;  // four shifted 16x16 SADs, 16 bits each (<= 65,280); shifts 0 and 2 are used
 #pragma unroll 4
         for (int r = 0; r < 16; ++r) {
             const int a = (dyr + r) * kWs4 + g;
             const uint32_t w0 = win32[a], w1 = win32[a + 1], w2 = win32[a + 2], w3 = win32[a + 3], w4 = win32[a + 4];
             const uint32_t s0 = srcw[r * 4 + 0], s1 = srcw[r * 4 + 1], s2 = srcw[r * 4 + 2], s3 = srcw[r * 4 + 3];
-            s0a = __builtin_amdgcn_sad_u8(w0, s0, s0a);
-            s0a = __builtin_amdgcn_sad_u8(w1, s1, s0a);
-            s0a = __builtin_amdgcn_sad_u8(w2, s2, s0a);
-            s0a = __builtin_amdgcn_sad_u8(w3, s3, s0a);
-            s2a = __builtin_amdgcn_sad_u8(__builtin_amdgcn_alignbyte(w1, w0, 2), s0, s2a);
-            s2a = __builtin_amdgcn_sad_u8(__builtin_amdgcn_alignbyte(w2, w1, 2), s1, s2a);
-            s2a = __builtin_amdgcn_sad_u8(__builtin_amdgcn_alignbyte(w3, w2, 2), s2, s2a);
-            s2a = __builtin_amdgcn_sad_u8(__builtin_amdgcn_alignbyte(w4, w3, 2), s3, s2a);
+            acc = qsad4(w1, w0, s0, acc);
+            acc = qsad4(w2, w1, s1, acc);
+            acc = qsad4(w3, w2, s2, acc);
+            acc = qsad4(w4, w3, s3, acc);
         }
+        const uint32_t s0a = (uint32_t)acc & 0xffffu, s2a = (uint32_t)(acc >> 32) & 0xffffu;
 #pragma unroll
         for (int h2 = 0; h2 < 2; ++h2) {
             const int dxr = 4 * g + 2 * h2;
@@ -436,26 +435,19 @@ __device__ __forceinline__ MbInfo me_full_body(const Geometry& g, const MeState&
     }
     for (int q = tid; q < ((coarse || parts) ? 0 : ngroups); q += kMeThreads) {
         const int dyr = q / gw, g = q - dyr * gw;
-        uint32_t sad[4] = {0, 0, 0, 0};
+        uint64_t acc = 0;  // four shifted 16x16 SADs, 16 bits each
 #pragma unroll 2
         for (int r = 0; r < 16; ++r) {
             const int a = (dyr + r) * kWs4 + g;
             const uint32_t w0 = win32[a], w1 = win32[a + 1], w2 = win32[a + 2], w3 = win32[a + 3], w4 = win32[a + 4];
             const uint32_t s0 = srcw[r * 4 + 0], s1 = srcw[r * 4 + 1], s2 = srcw[r * 4 + 2], s3 = srcw[r * 4 + 3];
-            sad[0] = __builtin_amdgcn_sad_u8(w0, s0, sad[0]);
-            sad[0] = __builtin_amdgcn_sad_u8(w1, s1, sad[0]);
-            sad[0] = __builtin_amdgcn_sad_u8(w2, s2, sad[0]);
-            sad[0] = __builtin_amdgcn_sad_u8(w3, s3, sad[0]);
-#pragma unroll
-            for (int sh = 1; sh < 4; ++sh) {
-                uint32_t t = sad[sh];
-                t = __builtin_amdgcn_sad_u8(__builtin_amdgcn_alignbyte(w1, w0, sh), s0, t);
-                t = __builtin_amdgcn_sad_u8(__builtin_amdgcn_alignbyte(w2, w1, sh), s1, t);
-                t = __builtin_amdgcn_sad_u8(__builtin_amdgcn_alignbyte(w3, w2, sh), s2, t);
-                t = __builtin_amdgcn_sad_u8(__builtin_amdgcn_alignbyte(w4, w3, sh), s3, t);
-                sad[sh] = t;
-            }
+            acc = qsad4(w1, w0, s0, acc);
+            acc = qsad4(w2, w1, s1, acc);
+            acc = qsad4(w3, w2, s2, acc);
+            acc = qsad4(w4, w3, s3, acc);
         }
+        const uint32_t sad[4] = {(uint32_t)acc & 0xffffu, (uint32_t)(acc >> 16) & 0xffffu,
+                                 (uint32_t)(acc >> 32) & 0xffffu, (uint32_t)(acc >> 48) & 0xffffu};
 #pragma unroll
         for (int sh = 0; sh < 4; ++sh) {
             const int dxr = 4 * g + sh;
