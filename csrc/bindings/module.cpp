@@ -180,6 +180,7 @@ PYBIND11_MODULE(_native, m) {
         .def_readwrite("qp_max", &h264::EncoderConfig::qp_max)
         .def_readwrite("keyint", &h264::EncoderConfig::keyint)
         .def_readwrite("search_range", &h264::EncoderConfig::search_range)
+        .def_readwrite("scroll_range", &h264::EncoderConfig::scroll_range)
         .def_readwrite("me_coarse", &h264::EncoderConfig::me_coarse)
         .def_readwrite("intra4x4", &h264::EncoderConfig::intra4x4)
         .def_readwrite("subpel", &h264::EncoderConfig::subpel)
@@ -216,7 +217,9 @@ PYBIND11_MODULE(_native, m) {
         .def_readonly("deblocked", &h264::FrameStats::deblocked)
         .def_readonly("db_coherent", &h264::FrameStats::db_coherent)
         .def_readonly("db_changed", &h264::FrameStats::db_changed)
-        .def_readonly("db_moving", &h264::FrameStats::db_moving);
+        .def_readonly("db_moving", &h264::FrameStats::db_moving)
+        .def_readonly("scroll_dx", &h264::FrameStats::scroll_dx)
+        .def_readonly("scroll_dy", &h264::FrameStats::scroll_dy);
 
     py::class_<h264::CpuH264Encoder>(m, "CpuH264Encoder")
         .def(py::init<const h264::EncoderConfig&>())
@@ -274,6 +277,22 @@ PYBIND11_MODULE(_native, m) {
                      std::memcpy(d + 9 * i, r, sizeof r);
                  }
                  return a.reshape({e.common().mb_h(), e.common().mb_w(), 9});
+             })
+        .def("mb_pmv",
+             [](h264::CpuH264Encoder& e) {  // (mb_h, mb_w, 4): the two partition vectors (part != 0)
+                 const auto& v = e.mb_info();
+                 py::array_t<int32_t> a({(py::ssize_t)v.size(), (py::ssize_t)4});
+                 int32_t* d = a.mutable_data();
+                 for (size_t i = 0; i < v.size(); ++i)
+                     for (int k = 0; k < 4; ++k) d[4 * i + k] = v[i].pmv[k];
+                 return a.reshape({e.common().mb_h(), e.common().mb_w(), 4});
+             })
+        .def("mb_scroll_path",
+             [](h264::CpuH264Encoder& e) {  // (mb_h, mb_w) of the last P picture: MeScrollPath per macroblock
+                 const auto& v = e.mb_scroll_path();
+                 py::array_t<uint8_t> a((py::ssize_t)v.size());
+                 std::memcpy(a.mutable_data(), v.data(), v.size());
+                 return a.reshape({e.common().mb_h(), e.common().mb_w()});
              })
         .def("request_idr", [](h264::CpuH264Encoder& e) { e.common().request_idr(); })
         .def("set_bitrate", [](h264::CpuH264Encoder& e, int k) { e.common().set_bitrate(k); })
@@ -714,6 +733,8 @@ PYBIND11_MODULE(_native, m) {
         .def_readonly("deblocked", &FrameResult::deblocked)
         .def_readonly("db_coherent", &FrameResult::db_coherent)
         .def_readonly("db_moving", &FrameResult::db_moving)
+        .def_readonly("scroll_dx", &FrameResult::scroll_dx)
+        .def_readonly("scroll_dy", &FrameResult::scroll_dy)
         .def_property_readonly("au", [](const FrameResult& r) { return to_bytes(r.au); });
 
     m.def(

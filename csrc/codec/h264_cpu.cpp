@@ -37,8 +37,48 @@ void pad_nv12(const uint8_t* y, const uint8_t* uv, int w, int h, int pitch, int 
 // Integer full search + quarter-pel refinement of the 16x16 block at (x0, y0): the same
 // rules as k_me_full (static-block exit, cost = SAD + lambda * mv bits, tie -> shorter vector
 // then lower candidate index).  Shared by the CPU H.264 and HEVC encoders.
+// 16x16 SAD at the integer vector (vx, vy), edge-clamped.
+static uint32_t sad16_at_cpu(const uint8_t* sy, int pitch, const uint8_t* ref_y, int cw, int ch, int x0, int y0, int vx,
+                             int vy) {
+    uint32_t sad = 0;
+    for (int r = 0; r < 16; ++r)
+        for (int k = 0; k < 16; ++k)
+            sad += (uint32_t)std::abs((int)sy[(y0 + r) * pitch + x0 + k] - ref_px(ref_y, cw, cw, ch, x0 + vx + k, y0 + vy + r));
+    return sad;
+}
+
+// The scroll probe pass (EncoderConfig::scroll_range; the rules of k_scroll_probe, h264_mb.h scroll_*):
+// every probe macroblock of the lattice whose zero vector is not static scores the 16x16 SAD of
+// every (0, d) and (d, 0), 0 < |d| <= D, and votes for its best when that is a static match.
+void scroll_probe_cpu(const uint8_t* sy, int pitch, const uint8_t* ref_y, int cw, int ch, int mb_w, int mb_h, int qp,
+                      int D, std::vector<uint32_t>& hist, int* gx, int* gy) {
+    hist.assign((size_t)scroll_bins(D), 0u);
+    for (int mby = 0; mby < mb_h; mby += kScrollLattice)
+        for (int mbx = 0; mbx < mb_w; mbx += kScrollLattice) {
+            const int x0 = mbx * 16, y0 = mby * 16;
+            if (sad16_at_cpu(sy, pitch, ref_y, cw, ch, x0, y0, 0, 0) <= static_sad(qp)) continue;
+            unsigned long long best = ~0ull;
+            for (int axis = 0; axis < 2; ++axis)
+                for (int d = -D; d <= D; ++d) {
+                    if (!d) continue;
+                    const uint32_t sad = sad16_at_cpu(sy, pitch, ref_y, cw, ch, x0, y0, axis ? d : 0, axis ? 0 : d);
+                    best = std::min(best, scroll_probe_key(sad, axis, d, D));
+                }
+            if (scroll_key_votes(best, qp)) ++hist[(size_t)scroll_key_bin(best)];
+        }
+    unsigned long long win = 0;
+    uint32_t total = 0;
+    for (int b = 0; b < scroll_bins(D); ++b) {
+        win = std::max(win, scroll_bin_key(hist[(size_t)b], b, D));
+        total += hist[(size_t)b];
+        hist[(size_t)b] = 0;
+    }
+    scroll_decide(win, total, D, gx, gy);
+}
+
 void me_search_cpu(const uint8_t* sy, int pitch, const uint8_t* ref_y, int cw_, int ch_, int x0, int y0,
-                   int frame_qp, int search_range, int subpel, int* out_mvx, int* out_mvy, int coarse) {
+                   int frame_qp, int search_range, int subpel, int* out_mvx, int* out_mvy, int coarse, int gx, int gy,
+                   uint8_t* path) {
     const int lambda = lambda_sad(frame_qp);
     const int R = me_range(search_range);
     const int side = 2 * R + 1;
@@ -48,6 +88,20 @@ void me_search_cpu(const uint8_t* sy, int pitch, const uint8_t* ref_y, int cw_, 
         for (int k = 0; k < 16; ++k)
             sad0 += std::abs((int)sy[(y0 + r) * pitch + x0 + k] - ref_px(ref_y, cw_, cw_, ch_, x0 + k, y0 + r));
     const bool is_static = sad0 <= static_sad(frame_qp);
+    // the centre (cx, cy) of the search: zero, or the picture's scroll hint (scroll_use).  Vectors
+    // below are local to it: the rate term of me_cost is taken relative to the centre
+    int cx = 0, cy = 0;
+    if (path) *path = is_static ? kPathStatic : kPathNoHint;
+    if (!is_static && (gx || gy)) {
+        const int use = scroll_use(sad16_at_cpu(sy, pitch, ref_y, cw_, ch_, x0, y0, gx, gy), sad0, frame_qp);
+        if (path) *path = use == kScrollExit ? kPathHintExit : (use == kScrollCentre ? kPathHintCentre : kPathHintZero);
+        if (use == kScrollExit) {
+            *out_mvx = 4 * gx;
+            *out_mvy = 4 * gy;
+            return;
+        }
+        if (use == kScrollCentre) cx = gx, cy = gy;
+    }
     unsigned long long best = ~0ull;
     auto key_of = [&](int c) {
         const int dy = c / side - R, dx = c % side - R;
@@ -55,7 +109,7 @@ void me_search_cpu(const uint8_t* sy, int pitch, const uint8_t* ref_y, int cw_, 
         for (int r = 0; r < 16; ++r)
             for (int k = 0; k < 16; ++k)
                 sad += std::abs((int)sy[(y0 + r) * pitch + x0 + k] -
-                                ref_px(ref_y, cw_, cw_, ch_, x0 + dx + k, y0 + dy + r));
+                                ref_px(ref_y, cw_, cw_, ch_, x0 + cx + dx + k, y0 + cy + dy + r));
         const uint32_t cost = me_cost(sad, lambda, 4 * dx, 4 * dy);
         const uint32_t dist = (uint32_t)(std::abs(dx) + std::abs(dy));
         return ((unsigned long long)cost << 32) | (dist << 16) | (uint32_t)c;
@@ -82,7 +136,7 @@ void me_search_cpu(const uint8_t* sy, int pitch, const uint8_t* ref_y, int cw_, 
             for (int r = 0; r < 16; ++r)
                 for (int k = 0; k < 16; ++k)
                     s += std::abs((int)sy[(y0 + r) * pitch + x0 + k] -
-                                  luma_qpel(ref_y, cw_, cw_, ch_, (x0 + k) * 4 + vx, (y0 + r) * 4 + vy));
+                                  luma_qpel(ref_y, cw_, cw_, ch_, (x0 + cx + k) * 4 + vx, (y0 + cy + r) * 4 + vy));
             return s;
         };
         uint32_t cur_cost = (uint32_t)(best >> 32);
@@ -92,8 +146,8 @@ void me_search_cpu(const uint8_t* sy, int pitch, const uint8_t* ref_y, int cw_, 
             for (int k = 0; k < 8; ++k) {
                 int ddx, ddy;
                 subpel_offset(k, &ddx, &ddy);
-                const int cx = mvx + ddx * step, cy = mvy + ddy * step;
-                const uint32_t cost = me_cost(sad_at(cx, cy), lambda, cx, cy);
+                const int qx = mvx + ddx * step, qy = mvy + ddy * step;
+                const uint32_t cost = me_cost(sad_at(qx, qy), lambda, qx, qy);
                 if (cost < bcost) {
                     bcost = cost;
                     bdx = ddx * step;
@@ -105,8 +159,8 @@ void me_search_cpu(const uint8_t* sy, int pitch, const uint8_t* ref_y, int cw_, 
             cur_cost = bcost;
         }
     }
-    *out_mvx = mvx;
-    *out_mvy = mvy;
+    *out_mvx = 4 * cx + mvx;
+    *out_mvy = 4 * cy + mvy;
 }
 
 // Partition-aware search (the rules of k_me_full with FrameState::partitions):
@@ -119,7 +173,8 @@ void me_search_cpu(const uint8_t* sy, int pitch, const uint8_t* ref_y, int cw_, 
 //  * quarter-pel refinement (half, then quarter) of the chosen shape's vector(s), each over its
 //    own rectangle.
 void me_search_parts_cpu(const uint8_t* sy, int pitch, const uint8_t* ref_y, int cw_, int ch_, int x0, int y0,
-                         int frame_qp, int search_range, int subpel, int coarse, MbInfo& m) {
+                         int frame_qp, int search_range, int subpel, int coarse, MbInfo& m, int gx, int gy,
+                         uint8_t* path) {
     const int lambda = lambda_sad(frame_qp);
     const int R = me_range(search_range);
     const int side = 2 * R + 1;
@@ -130,7 +185,20 @@ void me_search_parts_cpu(const uint8_t* sy, int pitch, const uint8_t* ref_y, int
     m.part = kPart16x16;
     m.mvx = m.mvy = 0;
     for (int i = 0; i < 4; ++i) m.pmv[i] = 0;
+    if (path) *path = kPathStatic;
     if (sad0 <= static_sad(frame_qp)) return;
+    if (path) *path = kPathNoHint;
+    int cx = 0, cy = 0;  // the centre of the search (me_search_cpu)
+    if (gx || gy) {
+        const int use = scroll_use(sad16_at_cpu(sy, pitch, ref_y, cw_, ch_, x0, y0, gx, gy), sad0, frame_qp);
+        if (path) *path = use == kScrollExit ? kPathHintExit : (use == kScrollCentre ? kPathHintCentre : kPathHintZero);
+        if (use == kScrollExit) {
+            m.mvx = (int16_t)(4 * gx);
+            m.mvy = (int16_t)(4 * gy);
+            return;
+        }
+        if (use == kScrollCentre) cx = gx, cy = gy;
+    }
     // shapes: 0 = 16x16, 1 = top, 2 = bottom, 3 = left, 4 = right (quadrants TL, TR, BL, BR)
     auto quads = [&](int c, uint32_t q[4]) {
         const int dy = c / side - R, dx = c % side - R;
@@ -138,7 +206,7 @@ void me_search_parts_cpu(const uint8_t* sy, int pitch, const uint8_t* ref_y, int
         for (int r = 0; r < 16; ++r)
             for (int k = 0; k < 16; ++k)
                 q[(r >= 8 ? 2 : 0) + (k >= 8 ? 1 : 0)] += (uint32_t)std::abs(
-                    (int)sy[(y0 + r) * pitch + x0 + k] - ref_px(ref_y, cw_, cw_, ch_, x0 + dx + k, y0 + dy + r));
+                    (int)sy[(y0 + r) * pitch + x0 + k] - ref_px(ref_y, cw_, cw_, ch_, x0 + cx + dx + k, y0 + cy + dy + r));
     };
     auto shape_sad = [](const uint32_t q[4], int s) {
         switch (s) {
@@ -195,12 +263,12 @@ void me_search_parts_cpu(const uint8_t* sy, int pitch, const uint8_t* ref_y, int
         *vy = 4 * ((cb / side) - R);
         if (!subpel) return;
         const int rx = kRect[s][0], ry = kRect[s][1], rw = kRect[s][2], rh = kRect[s][3];
-        auto sad_at = [&](int cx, int cy) {
+        auto sad_at = [&](int qx, int qy) {
             uint32_t t = 0;
             for (int r = ry; r < ry + rh; ++r)
                 for (int k = rx; k < rx + rw; ++k)
                     t += std::abs((int)sy[(y0 + r) * pitch + x0 + k] -
-                                  luma_qpel(ref_y, cw_, cw_, ch_, (x0 + k) * 4 + cx, (y0 + r) * 4 + cy));
+                                  luma_qpel(ref_y, cw_, cw_, ch_, (x0 + cx + k) * 4 + qx, (y0 + cy + r) * 4 + qy));
             return t;
         };
         uint32_t cur = cost_of(best[s]);
@@ -210,8 +278,8 @@ void me_search_parts_cpu(const uint8_t* sy, int pitch, const uint8_t* ref_y, int
             for (int k = 0; k < 8; ++k) {
                 int ddx, ddy;
                 subpel_offset(k, &ddx, &ddy);
-                const int cx = *vx + ddx * step, cy = *vy + ddy * step;
-                const uint32_t cost = me_cost(sad_at(cx, cy), lambda, cx, cy);
+                const int qx = *vx + ddx * step, qy = *vy + ddy * step;
+                const uint32_t cost = me_cost(sad_at(qx, qy), lambda, qx, qy);
                 if (cost < bcost) {
                     bcost = cost;
                     bdx = ddx * step;
@@ -226,19 +294,19 @@ void me_search_parts_cpu(const uint8_t* sy, int pitch, const uint8_t* ref_y, int
     int vx, vy;
     if (part == kPart16x16) {
         refine(0, &vx, &vy);
-        m.mvx = (int16_t)vx;
-        m.mvy = (int16_t)vy;
+        m.mvx = (int16_t)(4 * cx + vx);
+        m.mvy = (int16_t)(4 * cy + vy);
         return;
     }
     const int cb = (int)(best[0] & 0xffff);  // the 16x16 vector stays integer here
-    m.mvx = (int16_t)(4 * ((cb % side) - R));
-    m.mvy = (int16_t)(4 * ((cb / side) - R));
+    m.mvx = (int16_t)(4 * (cx + (cb % side) - R));
+    m.mvy = (int16_t)(4 * (cy + (cb / side) - R));
     m.part = (uint8_t)part;
     const int s0 = part == kPart16x8 ? 1 : 3;
     for (int i = 0; i < 2; ++i) {
         refine(s0 + i, &vx, &vy);
-        m.pmv[2 * i] = (int16_t)vx;
-        m.pmv[2 * i + 1] = (int16_t)vy;
+        m.pmv[2 * i] = (int16_t)(4 * cx + vx);
+        m.pmv[2 * i + 1] = (int16_t)(4 * cy + vy);
     }
 }
 
@@ -430,6 +498,13 @@ void CpuH264Encoder::encode_inter(const uint8_t* sy, const uint8_t* suv, int pit
     uint8_t* rec_y = rec_y_[cur_].data();
     uint8_t* rec_uv = rec_uv_[cur_].data();
     const int frame_qp = frame_qp_();
+    // scroll hint: the probe pass reads what the search reads
+    int gx = 0, gy = 0;
+    if (const int D = scroll_reach(cfg_.scroll_range))
+        scroll_probe_cpu(sy, pitch, me_ref, cw_, ch_, g.mb_w, g.mb_h, frame_qp, D, scroll_hist_, &gx, &gy);
+    stats_.scroll_dx = gx;
+    stats_.scroll_dy = gy;
+    mb_path_.assign(mb_.size(), (uint8_t)kPathStatic);
     for (int mby = 0; mby < g.mb_h; ++mby)
         for (int mbx = 0; mbx < g.mb_w; ++mbx) {
             const int mbi = mby * g.mb_w + mbx, x0 = mbx * 16, y0 = mby * 16;
@@ -437,11 +512,11 @@ void CpuH264Encoder::encode_inter(const uint8_t* sy, const uint8_t* suv, int pit
             std::memset(&m, 0, sizeof m);
             if (cfg_.partitions) {
                 me_search_parts_cpu(sy, pitch, me_ref, cw_, ch_, x0, y0, frame_qp, cfg_.search_range, cfg_.subpel,
-                                    cfg_.me_coarse, m);
+                                    cfg_.me_coarse, m, gx, gy, &mb_path_[mbi]);
             } else {
                 int vx = 0, vy = 0;
                 me_search_cpu(sy, pitch, me_ref, cw_, ch_, x0, y0, frame_qp, cfg_.search_range, cfg_.subpel, &vx, &vy,
-                              cfg_.me_coarse);
+                              cfg_.me_coarse, gx, gy, &mb_path_[mbi]);
                 m.mvx = (int16_t)vx;
                 m.mvy = (int16_t)vy;
             }
@@ -677,6 +752,7 @@ const std::vector<uint8_t>& CpuH264Encoder::encode(const uint8_t* y, const uint8
             for (int r = 0; r < ch; ++r) std::memcpy(d.data() + (size_t)r * cw, y + (size_t)r * pitch, cw);
         }
     } save_src{prev_src_, y, pitch, cw_, ch_};
+    stats_.scroll_dx = stats_.scroll_dy = 0;  // encode_inter: the P picture's hint
     if (common_.cur_idr())
         encode_intra(y, uv, pitch);
     else

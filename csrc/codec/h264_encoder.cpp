@@ -293,6 +293,14 @@ void GpuH264Encoder::alloc_slot(FrameSlot& sl) {
     HIP_CHECK(hipMemsetAsync(b.pack_done, 0, sizeof(uint32_t), stream_));
     HIP_CHECK(hipMalloc(&b.db_cnt, sizeof(uint32_t) * 4));
     HIP_CHECK(hipMemsetAsync(b.db_cnt, 0, sizeof(uint32_t) * 4, stream_));
+    if (const int D = scroll_reach(cfg_.scroll_range)) {  // vote histogram, hint
+        const size_t hist_bytes = sizeof(uint32_t) * (size_t)scroll_bins(D);
+        sl.scroll.reach = D;
+        HIP_CHECK(hipMalloc(&sl.scroll.hist, hist_bytes));
+        HIP_CHECK(hipMemsetAsync(sl.scroll.hist, 0, hist_bytes, stream_));
+        HIP_CHECK(hipMalloc(&sl.scroll.hint, sizeof(int32_t) * 2));
+        HIP_CHECK(hipMemsetAsync(sl.scroll.hint, 0, sizeof(int32_t) * 2, stream_));
+    }
     HIP_CHECK(hipHostMalloc(&b.db_err, sizeof(int), hipHostMallocMapped));
     *b.db_err = 0;
     HIP_CHECK(hipHostMalloc(&sl.fs_host, sizeof(FrameState), hipHostMallocDefault));
@@ -310,7 +318,8 @@ void GpuH264Encoder::free_slot(FrameSlot& sl) {
     for (void* p : {(void*)b.fs, (void*)b.mb, (void*)b.coef, (void*)b.slot, (void*)b.slot_bits, (void*)b.row_agg,
                     (void*)b.row_sse, (void*)b.coded_info, (void*)b.slice_info,
                     (void*)b.out_hdr, (void*)b.sse_part, (void*)b.wave_prog, (void*)b.mb_sse, (void*)b.intra_gain, (void*)b.intra_cand, (void*)b.quad_unit,
-                    (void*)b.db_rec, (void*)b.db_rowq, (void*)b.db_glb, (void*)b.pack_done, (void*)b.db_cnt})
+                    (void*)b.db_rec, (void*)b.db_rowq, (void*)b.db_glb, (void*)b.pack_done, (void*)b.db_cnt,
+                    (void*)sl.scroll.hist, (void*)sl.scroll.hint})
         if (p) (void)hipFree(p);
     if (b.db_err) (void)hipHostFree(b.db_err);
     if (sl.fs_host) (void)hipHostFree(sl.fs_host);
@@ -413,7 +422,7 @@ void GpuH264Encoder::launcher_loop() {
         try {
             FrameSlot& sl = slots_[j.slot];
             HIP_CHECK(hipStreamWaitEvent(j.stream, sl.analysis_done, 0));
-            launch_entropy(geom_, sl.buf, sl.host_out, j.stream, j.sse_ready);
+            launch_entropy(geom_, sl.buf, sl.host_out, j.stream, j.sse_ready, sl.scroll.hint);
             HIP_CHECK(hipGetLastError());
             HIP_CHECK(hipEventRecord(sl.done, j.stream));
         } catch (...) {
@@ -494,23 +503,29 @@ void GpuH264Encoder::enqueue_analysis_kernels(bool idr, const uint8_t* src_y, co
         // the picture's first kernel: it publishes the frame state on whichever stream it runs
         if (depth_ > 1 && pub && sl.me_unf) ensure_me_stream();
         const bool side_me = stream_m_ && pub && sl.me_unf;
+        // scroll hint: the probe pass goes before the search on the search's stream and is then the
+        // picture's first kernel (it publishes the state and stamps the start)
+        const ScrollBuffers* scroll = sl.scroll.reach ? &sl.scroll : nullptr;
         if (side_me) {
             HIP_CHECK(hipStreamWaitEvent(stream_m_, ev_hpu_, 0));
             if (in_ev_) {
                 HIP_CHECK(hipStreamWaitEvent(stream_m_, in_ev_, 0));
                 in_ev_ = nullptr;  // the analysis stream waits for the search, so for the input too
             }
-            launch_me(geom_, sl.buf, src_y, stream_m_, pub, true);
+            if (scroll) launch_scroll_probe(geom_, sl.buf, *scroll, src_y, stream_m_, pub);
+            launch_me(geom_, sl.buf, src_y, stream_m_, pub, true, scroll);
             HIP_CHECK(hipEventRecord(sl.me_done, stream_m_));
             HIP_CHECK(hipStreamWaitEvent(stream_, sl.me_done, 0));
             launch_inter(geom_, sl.buf, src_y, src_uv, stream_);
         } else if (!sl.me_unf && geom_.mb_w * geom_.mb_h <= kFusedMaxMbs) {
             // the search reads the picture the coder predicts from: one kernel searches and codes
             wait_input();
-            launch_p_fused(geom_, sl.buf, src_y, src_uv, stream_, pub);
+            if (scroll) launch_scroll_probe(geom_, sl.buf, *scroll, src_y, stream_, pub);
+            launch_p_fused(geom_, sl.buf, src_y, src_uv, stream_, pub, scroll);
         } else {
             wait_input();
-            launch_me(geom_, sl.buf, src_y, stream_, pub);
+            if (scroll) launch_scroll_probe(geom_, sl.buf, *scroll, src_y, stream_, pub);
+            launch_me(geom_, sl.buf, src_y, stream_, pub, false, scroll);
             launch_inter(geom_, sl.buf, src_y, src_uv, stream_);
         }
         if (cfg_.intra_in_p) launch_intra_in_p(geom_, sl.buf, src_y, src_uv, stream_);
@@ -528,7 +543,7 @@ void GpuH264Encoder::link_entropy() {
 void GpuH264Encoder::enqueue_entropy() {
     drain_launcher();
     FrameSlot& sl = slots_[prep_slot_];
-    launch_entropy(geom_, sl.buf, sl.host_out, stream_e_ ? stream_e_ : stream_, nullptr);
+    launch_entropy(geom_, sl.buf, sl.host_out, stream_e_ ? stream_e_ : stream_, nullptr, sl.scroll.hint);
 }
 
 void GpuH264Encoder::unfiltered_copy(FrameSlot& sl) {
@@ -577,7 +592,7 @@ void GpuH264Encoder::enqueue_kernels(bool idr, const uint8_t* src_y, const uint8
             sse_ready = sl.deblock_done;
         }
     }
-    launch_entropy(geom_, sl.buf, sl.host_out, es, sse_ready);
+    launch_entropy(geom_, sl.buf, sl.host_out, es, sse_ready, sl.scroll.hint);
     HIP_CHECK(hipGetLastError());
 }
 
@@ -743,6 +758,8 @@ const std::vector<uint8_t>& GpuH264Encoder::collect() {
     stats_.db_coherent = (int)hdr.db_coherent;
     stats_.db_changed = (int)hdr.db_changed;
     stats_.db_moving = (int)hdr.db_moving;
+    stats_.scroll_dx = hdr.scroll_dx;
+    stats_.scroll_dy = hdr.scroll_dy;
     // picture fidx + kDbLag's filter, from this one's classes
     db_lag_.record((long long)sl.fidx, sl.idr, DbAutoCounts{hdr.db_coherent, hdr.db_changed, hdr.db_moving},
                    geom_.mb_w * geom_.mb_h);

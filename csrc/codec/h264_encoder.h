@@ -37,6 +37,13 @@ struct EncoderConfig {
     int qp_max = 46;
     int keyint = 0;           // IDR period in frames, 0 = only on demand (infinite GOP)
     int search_range = 16;    // integer-pel full search radius (<= 32)
+    // H.264 P pictures: the largest scroll looked for, in luma samples; 0 = off.  A probe pass finds at
+    // most one axis-aligned displacement per picture (h264_mb.h scroll_*), and a macroblock may centre
+    // its +-search_range search on it instead of on zero.  Clamped to [0, 192] and rounded up to a
+    // multiple of 4 (scroll_reach): 192 + 32 (largest search radius) + 1 (sub-sample refinement)
+    // stays inside the vertical vector range [-256, +255.75] of level 3.0, the lowest level
+    // pick_level() signals, so every vector is legal at every level the encoder can signal
+    int scroll_range = 0;
     int intra4x4 = 1;         // Intra4x4 allowed for intra MBs (0: Intra16x16 only -- cheaper IDR wavefront)
     int me_coarse = 0;        // 1: ME over the even-offset grid + the 8 integer neighbours of its best (4x
                               // fewer SADs: +5.7 % fps, -0.4 dB masked Y-PSNR at 8 Mbps, profiles/r02_me);
@@ -132,6 +139,7 @@ struct FrameStats {
     int64_t masked_pixels = 0;    // display luma samples outside them (the PSNR denominator)
     int deblocked = 0;            // the in-loop filter ran on this picture (H.264 idc 0, HEVC, VP8 level > 0)
     int db_coherent = 0, db_changed = 0, db_moving = 0;  // adaptive filter: the picture's class counts (db_auto_count)
+    int scroll_dx = 0, scroll_dy = 0;  // the scroll hint used for this picture, full samples (0, 0: none)
 };
 
 // Annex-B / rate-control logic shared by both encoders.
@@ -305,6 +313,7 @@ class GpuH264Encoder final : public VideoEncoder {
         int qp = 0;
         uint64_t fidx = 0;     // picture number (seq_ when prepared)
         hipEvent_t me_done = nullptr;  // the side-stream motion search of this picture
+        ScrollBuffers scroll;          // scroll hint of this slot's picture (EncoderConfig::scroll_range)
     };
     void alloc_slot(FrameSlot& sl);
     void free_slot(FrameSlot& sl);
@@ -397,6 +406,8 @@ class CpuH264Encoder {
     // analysis hooks: per-MB coded bits of the last frame (0 = skipped) and the MB records
     const std::vector<uint32_t>& mb_bits() const { return mb_bits_; }
     const std::vector<MbInfo>& mb_info() const { return mb_; }
+    // per MB of the last P picture: how its search used the scroll hint (MeScrollPath)
+    const std::vector<uint8_t>& mb_scroll_path() const { return mb_path_; }
 
    private:
     void encode_intra(const uint8_t* y, const uint8_t* uv, int pitch);
@@ -424,6 +435,8 @@ class CpuH264Encoder {
     std::vector<MbInfo> mb_;
     std::vector<int16_t> coef_;
     std::vector<uint32_t> mb_bits_;
+    std::vector<uint8_t> mb_path_;
+    std::vector<uint32_t> scroll_hist_;  // the probe pass's vote histogram (scroll_bins)
     std::vector<uint8_t> prev_src_;  // previous source luma (coded size), temporal AQ classes
     std::vector<uint8_t> au_;
     FrameStats stats_;
@@ -431,12 +444,27 @@ class CpuH264Encoder {
 
 // CPU motion search of one 16x16 block (same rules as the GPU k_me_full); shared by the
 // CPU H.264 and HEVC encoders.
+// (gx, gy): the picture's scroll hint in full samples (H.264 only; h264_mb.h scroll_use); path, when
+// given, receives the MeScrollPath the macroblock took.
+enum MeScrollPath : uint8_t {
+    kPathStatic = 0,     // zero-vector static exit (the hint is never looked at)
+    kPathNoHint = 1,     // searched around zero, no hint for the picture
+    kPathHintExit = 2,   // took vector 4g without a search
+    kPathHintCentre = 3, // searched around g
+    kPathHintZero = 4,   // a hint, but searched around zero
+};
 void me_search_cpu(const uint8_t* sy, int pitch, const uint8_t* ref_y, int cw, int ch, int x0, int y0, int qp,
-                   int search_range, int subpel, int* mvx, int* mvy, int coarse);
+                   int search_range, int subpel, int* mvx, int* mvy, int coarse, int gx = 0, int gy = 0,
+                   uint8_t* path = nullptr);
 // The same search plus 16x8 / 8x16 partitionings (k_me_full with FrameState::partitions): writes
 // m.mvx / mvy (best 16x16 vector), m.part and m.pmv.
 void me_search_parts_cpu(const uint8_t* sy, int pitch, const uint8_t* ref_y, int cw, int ch, int x0, int y0, int qp,
-                         int search_range, int subpel, int coarse, MbInfo& m);
+                         int search_range, int subpel, int coarse, MbInfo& m, int gx = 0, int gy = 0,
+                         uint8_t* path = nullptr);
+// The scroll probe pass of a P picture (the rules of k_scroll_probe): votes of the lattice's probe
+// macroblocks into hist (scroll_bins(D) zeroed bins, cleared again on return) and the decision.
+void scroll_probe_cpu(const uint8_t* sy, int pitch, const uint8_t* ref_y, int cw, int ch, int mb_w, int mb_h, int qp,
+                      int D, std::vector<uint32_t>& hist, int* gx, int* gy);
 
 // Pad a display-sized NV12 frame to the coded size by edge replication (what the CSC
 // kernel does on the GPU side).  Returns pitch = coded width.

@@ -1,7 +1,7 @@
 // Device data layout and host API of the HIP H.264 encoder.
 //
 // Per-frame kernel chain (all on one HIP stream, graph-capturable):
-//   P frame: k_p_fused (or k_me_full -> k_inter_encode when the search runs on the unfiltered
+//   P frame: [k_scroll_probe -> k_scroll_decide, with EncoderConfig::scroll_range ->] k_p_fused (or k_me_full -> k_inter_encode when the search runs on the unfiltered
 //            copy of a deblocked reference) -> k_intra_analyze -> k_intra_p (intra_in_p)
 //            -> k_cavlc -> k_scan_rows -> k_scan_out -> k_pack
 // Both P-frame kernels interpolate the reference's sub-sample positions themselves, from windows of
@@ -128,7 +128,7 @@ struct OutHeader {
     // adaptive filter (EncoderConfig::deblock 2): the P picture's class counts (h264_deblock.h
     // db_auto_count, k_scan_rows), from which the host decides the next picture's filter
     uint32_t db_coherent, db_changed, db_moving;
-    uint32_t pad;
+    int16_t scroll_dx, scroll_dy;  // the scroll hint the P picture's search used (k_scan_out; 0, 0: none)
 };
 static_assert(sizeof(OutHeader) % 16 == 0, "payload must stay 16-byte aligned");
 constexpr int kMaxSlices = 1024;
@@ -174,6 +174,15 @@ struct DeviceBuffers {
     uint32_t* db_cnt;       // [3] adaptive filter: coherent / changed / moving counts (k_scan_rows, zeroed by k_scan_out)
     uint32_t* pack_done;    // [1] k_pack workgroups finished (the last one stamps t_end and resets it)
 };
+// Scroll hint (H.264 P pictures, EncoderConfig::scroll_range; h264_mb.h scroll_*): the buffers of one
+// frame slot -- per slot, since the entropy stage of picture n reads the hint while the probe of
+// picture n + 1 may already run.  The kernels take them as arguments: FrameState and DeviceBuffers,
+// which the HEVC and VP8 encoders share, are what they were.
+struct ScrollBuffers {
+    uint32_t* hist = nullptr;  // [scroll_bins(reach)] vote histogram, all zero between pictures
+    int32_t* hint = nullptr;   // [2] gx, gy (full samples) the probe pass leaves for the search
+    int reach = 0;             // scroll_reach(scroll_range); 0: off, nothing allocated
+};
 
 // Kernel launchers (h264_kernels.hip).  All enqueue on `stream`; no host sync.
 // The search is the first kernel of an H.264 P picture: with `publish` non-null it takes the state
@@ -181,8 +190,16 @@ struct DeviceBuffers {
 // reads b.fs (a memcpy node under hipGraph; the HEVC / VP8 encoders' own publication).
 // side: the launch goes to the side stream beside the reference's in-loop filter (k_me_full_val, the
 // same body under another name so that a kernel trace tells the two apart).
+// scroll: launch_scroll_probe went before on this stream -- it was the picture's first kernel and
+// stamped the start -- and the search may centre on scroll->hint (an instantiation of its own:
+// without the hint the kernels are what they were).
 void launch_me(const Geometry& g, const DeviceBuffers& b, const uint8_t* src_y, hipStream_t stream,
-               const FrameState* publish = nullptr, bool side = false);
+               const FrameState* publish = nullptr, bool side = false, const ScrollBuffers* scroll = nullptr);
+// The scroll probe pass of a P picture: votes of the lattice's probe macroblocks (k_scroll_probe) and
+// the decision into sb.hint (k_scroll_decide).  The picture's first kernel: `publish` as
+// launch_me.  Reads the source and the reference the search reads.
+void launch_scroll_probe(const Geometry& g, const DeviceBuffers& b, const ScrollBuffers& sb, const uint8_t* src_y,
+                         hipStream_t stream, const FrameState* publish = nullptr);
 // Copy of a luma picture (the unfiltered reconstruction of a picture the in-loop filter is about to
 // modify) for the next picture's motion search (FrameState::me_ref)
 void launch_copy_luma(const Geometry& g, const uint8_t* luma, uint8_t* dst, hipStream_t stream);
@@ -200,7 +217,7 @@ void launch_inter(const Geometry& g, const DeviceBuffers& b, const uint8_t* src_
 // profiles/p_fused/NOTES.md).
 constexpr int kFusedMaxMbs = 8160;
 void launch_p_fused(const Geometry& g, const DeviceBuffers& b, const uint8_t* src_y, const uint8_t* src_uv,
-                    hipStream_t stream, const FrameState* publish = nullptr);
+                    hipStream_t stream, const FrameState* publish = nullptr, const ScrollBuffers* scroll = nullptr);
 // The first kernel of a frame (launch_intra for I, launch_me / launch_p_fused for P) publishes the frame
 // state: with `publish` non-null it takes the state by value and stores it to b.fs for the
 // later kernels (no copy node); with nullptr it reads b.fs (filled by a memcpy node, hipGraph).
@@ -222,8 +239,9 @@ void launch_deblock(const Geometry& g, const DeviceBuffers& b, const uint8_t* sr
 void launch_save_src(const Geometry& g, const DeviceBuffers& b, const uint8_t* src_y, hipStream_t stream);
 // wait_for_sse: event the stream waits on after k_cavlc, before the distortion partials are
 // reduced (the deblocking kernels' completion on the analysis stream), or nullptr
+// scroll_hint: the P picture's hint (ScrollBuffers::hint) for OutHeader::scroll_dx / dy, or nullptr
 void launch_entropy(const Geometry& g, const DeviceBuffers& b, uint8_t* host_out, hipStream_t stream,
-                    hipEvent_t wait_for_sse = nullptr);
+                    hipEvent_t wait_for_sse = nullptr, const int32_t* scroll_hint = nullptr);
 // P pictures, after launch_inter: open-loop intra analysis of every MB (intra vs inter) and the
 // closed-loop reconstruction of the MBs that switched to intra.
 void launch_intra_in_p(const Geometry& g, const DeviceBuffers& b, const uint8_t* src_y, const uint8_t* src_uv,

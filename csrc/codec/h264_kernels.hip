@@ -5,6 +5,10 @@
 //                   in LDS and every lane scores (2R+1)^2/256 integer candidates, four
 //                   horizontally adjacent ones per v_qsad_pk_u16_u8, then optional
 //                   quarter-pel refinement; block-wide argmin via shuffles + LDS.
+//  * k_scroll_probe / k_scroll_decide  (EncoderConfig::scroll_range) one workgroup per probe
+//                   macroblock scores the 1-D displacements up to the reach and votes; one
+//                   workgroup decides the picture's scroll hint, which the _scroll
+//                   instantiations of the search kernels may centre their window on.
 //  * k_inter_encode one wave per macroblock (4 per workgroup): motion compensation
 //                   (6-tap qpel / bilinear chroma), 4x4 integer transform, quantisation,
 //                   reconstruction into the reference frame.  Fully parallel over MBs.  A
@@ -258,8 +262,15 @@ __device__ __forceinline__ MeState me_state(const FrameState& f) {
 }
 // Returns the motion it stored in mbs[mbi] (mvx, mvy, part, pmv; the same on every thread): the
 // fused kernel codes the macroblock from it without reading it back.  win_lds: kWinWords of LDS.
+// kScroll (H.264 with EncoderConfig::scroll_range): a macroblock that fails the static exit looks at
+// the picture's scroll hint g (h264_mb.h scroll_use) and takes vector 4g outright, or builds its
+// window, candidates and footprints around the centre g instead of zero.  Vectors inside the body
+// stay local to the centre -- so does the rate term of me_cost -- and the centre is added to what
+// is stored.  Without kScroll the centre is the constant zero and the body is what it was.
+template <bool kScroll>
 __device__ __forceinline__ MbInfo me_full_body(const Geometry& g, const MeState& st, const uint8_t* __restrict__ src_y,
-                                               MbInfo* __restrict__ mbs, uint32_t* win_lds) {
+                                               MbInfo* __restrict__ mbs, uint32_t* win_lds,
+                                               const int32_t* __restrict__ hint = nullptr) {
     MbInfo out;
     out.mvx = out.mvy = 0;
     out.part = kPart16x16;
@@ -285,6 +296,7 @@ __device__ __forceinline__ MbInfo me_full_body(const Geometry& g, const MeState&
     // never load the search window (a separate static pre-pass kernel feeding a list of the
     // moving MBs was measured slower: its atomic list append serialises, profiles/r02_me)
     constexpr int kWs4 = kWinStride / 4;
+    int cx = 0, cy = 0;  // the centre of the search, full samples
     {
         if (tid < 64) {  // one wave: a dword of source and reference per lane, v_sad_u8
             const int r = tid >> 2, c4 = (tid & 3) * 4;
@@ -305,12 +317,41 @@ __device__ __forceinline__ MbInfo me_full_body(const Geometry& g, const MeState&
             }
             return out;  // uniform across the workgroup
         }
+        if constexpr (kScroll) {
+            const int gx = hint[0], gy = hint[1];  // uniform (k_scroll_decide's, the kernel before)
+            if (gx | gy) {
+                if (tid < 64) {  // one wave: the 16x16 SAD at the integer vector g, edge-clamped
+                    const int r = tid >> 2, c4 = (tid & 3) * 4;
+                    const uint32_t sw = *reinterpret_cast<const uint32_t*>(src_y + (y0 + r) * g.pitch + x0 + c4);
+                    uint32_t rw = 0;
+                    for (int k = 0; k < 4; ++k)
+                        rw |= (uint32_t)ref_px(ref, g.pitch, g.coded_w, g.coded_h, x0 + gx + c4 + k, y0 + gy + r) << (8 * k);
+                    const int d = wave_sum((int)__builtin_amdgcn_sad_u8(sw, rw, 0u));
+                    if (tid == 0) s_sad0[1] = (uint32_t)d;
+                }
+                __syncthreads();
+                const int use = scroll_use(s_sad0[1], sad0, st.qp);
+                if (use == kScrollExit) {
+                    if (tid == 0) {
+                        MbInfo& m = mbs[mbi];
+                        m.mvx = (int16_t)(4 * gx);
+                        m.mvy = (int16_t)(4 * gy);
+                        m.part = kPart16x16;
+                        m.pmv[0] = m.pmv[1] = m.pmv[2] = m.pmv[3] = 0;
+                    }
+                    out.mvx = (int16_t)(4 * gx);
+                    out.mvy = (int16_t)(4 * gy);
+                    return out;  // uniform
+                }
+                if (use == kScrollCentre) cx = gx, cy = gy;
+            }
+        }
     }
     // search window straight from the reference picture, edge-clamped.  Its left edge x0 - R - 4 is
     // a multiple of 4 and so is the coded width: a window dword lies wholly inside a picture row
     // (one dword load) or wholly beside it (the row's edge sample four times) -- no byte gathers.
     const bool t256 = tid < 256;  // the threads of the 256-thread refinement layouts
-    const int wrows = W + 2 * kWinPadY + 1, wx0 = x0 - R - kWinPadX, wy0 = y0 - R - kWinPadY;
+    const int wrows = W + 2 * kWinPadY + 1, wx0 = x0 + cx - R - kWinPadX, wy0 = y0 + cy - R - kWinPadY;
     const bool dwords = (g.pitch & 3) == 0 && (reinterpret_cast<uintptr_t>(ref) & 3) == 0;
     for (int i = tid; i < wrows * kWs4; i += kMeThreads) {
         const int wy = i / kWs4, wx4 = (i - wy * kWs4) * 4;
@@ -318,7 +359,9 @@ __device__ __forceinline__ MbInfo me_full_body(const Geometry& g, const MeState&
         if (wx4 < W + 2 * kWinPadX) {
             const int py = min(max(wy0 + wy, 0), g.coded_h - 1), px = wx0 + wx4;
             const uint8_t* row = ref + (size_t)py * g.pitch;
-            if (px < 0)
+            if (kScroll && (wx0 & 3))  // a centre off the dword grid: a dword may straddle the picture's edge
+                for (int k = 0; k < 4; ++k) w |= (uint32_t)row[min(max(px + k, 0), g.coded_w - 1)] << (8 * k);
+            else if (px < 0)
                 w = row[0] * 0x01010101u;
             else if (px >= g.coded_w)
                 w = row[g.coded_w - 1] * 0x01010101u;
@@ -608,21 +651,21 @@ __device__ __forceinline__ MbInfo me_full_body(const Geometry& g, const MeState&
             }
             if (tid == 0) {
                 MbInfo& m = mbs[mbi];
-                m.mvx = (int16_t)mvx;  // the integer 16x16 vector (unused by the partitioned MB)
-                m.mvy = (int16_t)mvy;
+                m.mvx = (int16_t)(4 * cx + mvx);  // the integer 16x16 vector (unused by the partitioned MB)
+                m.mvy = (int16_t)(4 * cy + mvy);
                 m.part = (uint8_t)part;
-                m.pmv[0] = (int16_t)pvx[0];
-                m.pmv[1] = (int16_t)pvy[0];
-                m.pmv[2] = (int16_t)pvx[1];
-                m.pmv[3] = (int16_t)pvy[1];
+                m.pmv[0] = (int16_t)(4 * cx + pvx[0]);
+                m.pmv[1] = (int16_t)(4 * cy + pvy[0]);
+                m.pmv[2] = (int16_t)(4 * cx + pvx[1]);
+                m.pmv[3] = (int16_t)(4 * cy + pvy[1]);
             }
-            out.mvx = (int16_t)mvx;
-            out.mvy = (int16_t)mvy;
+            out.mvx = (int16_t)(4 * cx + mvx);
+            out.mvy = (int16_t)(4 * cy + mvy);
             out.part = (uint8_t)part;
-            out.pmv[0] = (int16_t)pvx[0];
-            out.pmv[1] = (int16_t)pvy[0];
-            out.pmv[2] = (int16_t)pvx[1];
-            out.pmv[3] = (int16_t)pvy[1];
+            out.pmv[0] = (int16_t)(4 * cx + pvx[0]);
+            out.pmv[1] = (int16_t)(4 * cy + pvy[0]);
+            out.pmv[2] = (int16_t)(4 * cx + pvx[1]);
+            out.pmv[3] = (int16_t)(4 * cy + pvy[1]);
             return out;  // uniform
         }
     }
@@ -674,13 +717,13 @@ __device__ __forceinline__ MbInfo me_full_body(const Geometry& g, const MeState&
     }
     if (tid == 0) {
         MbInfo& m = mbs[mbi];
-        m.mvx = (int16_t)mvx;
-        m.mvy = (int16_t)mvy;
+        m.mvx = (int16_t)(4 * cx + mvx);
+        m.mvy = (int16_t)(4 * cy + mvy);
         m.part = kPart16x16;
         m.pmv[0] = m.pmv[1] = m.pmv[2] = m.pmv[3] = 0;
     }
-    out.mvx = (int16_t)mvx;
-    out.mvy = (int16_t)mvy;
+    out.mvx = (int16_t)(4 * cx + mvx);
+    out.mvy = (int16_t)(4 * cy + mvy);
     return out;
 }
 
@@ -692,13 +735,185 @@ __global__ __launch_bounds__(kMeThreads) void k_me_full(Geometry g, StateArg sa,
                                                         MbInfo* __restrict__ mbs) {
     __shared__ uint32_t win_lds[kWinWords];
     publish_state(sa);
-    me_full_body(g, sa.publish ? me_state(sa.v) : me_state(*sa.dst), src_y, mbs, win_lds);
+    me_full_body<false>(g, sa.publish ? me_state(sa.v) : me_state(*sa.dst), src_y, mbs, win_lds);
 }
 __global__ __launch_bounds__(kMeThreads) void k_me_full_val(Geometry g, StateArg sa, const uint8_t* __restrict__ src_y,
                                                             MbInfo* __restrict__ mbs) {
     __shared__ uint32_t win_lds[kWinWords];
     publish_state(sa);
-    me_full_body(g, me_state(sa.v), src_y, mbs, win_lds);
+    me_full_body<false>(g, me_state(sa.v), src_y, mbs, win_lds);
+}
+// The same two with the scroll hint (H.264 pictures after k_scroll_probe, which stamped the start)
+__global__ __launch_bounds__(kMeThreads) void k_me_full_scroll(Geometry g, StateArg sa,
+                                                               const uint8_t* __restrict__ src_y,
+                                                               MbInfo* __restrict__ mbs,
+                                                               const int32_t* __restrict__ hint) {
+    __shared__ uint32_t win_lds[kWinWords];
+    publish_state(sa);
+    me_full_body<true>(g, sa.publish ? me_state(sa.v) : me_state(*sa.dst), src_y, mbs, win_lds, hint);
+}
+__global__ __launch_bounds__(kMeThreads) void k_me_full_val_scroll(Geometry g, StateArg sa,
+                                                                   const uint8_t* __restrict__ src_y,
+                                                                   MbInfo* __restrict__ mbs,
+                                                                   const int32_t* __restrict__ hint) {
+    __shared__ uint32_t win_lds[kWinWords];
+    publish_state(sa);
+    me_full_body<true>(g, me_state(sa.v), src_y, mbs, win_lds, hint);
+}
+
+// ------------------------------------------------------------------ scroll probe
+// One 256-thread workgroup per probe macroblock of the lattice (h264_mb.h scroll_is_probe), before
+// the search of a P picture with EncoderConfig::scroll_range.  A probe whose zero vector passes the
+// static exit does nothing.  Every other one stages two edge-clamped strips of the reference in
+// LDS -- 16 wide x (16 + 2D) tall and (16 + 2D) wide x 16 tall, whole dwords as the search window --
+// and scores the 16x16 SAD of every (0, d) and (d, 0), 0 < |d| <= D: the vertical candidates one
+// per thread (v_sad_u8 on the four dwords of a row), the horizontal ones four per v_qsad_pk_u16_u8
+// as the search does, a thread per dword group and half of the rows.  The best candidate by
+// scroll_probe_key votes for its bin when it is a static match (integer atomics: the histogram
+// does not depend on the order).  k_scroll_decide, one workgroup after it, takes the decision
+// (scroll_bin_key, scroll_decide), stores the hint and leaves the histogram zero for the slot's next
+// picture.  (The decision in the probe's last workgroup, behind a counter as k_pack's, needs the
+// votes ordered before the count -- a release per workgroup: it added 55 us to a still 1080p
+// picture, where every probe leaves at once, against 21 us for the two kernels (13 + 5 us of
+// kernel time): profiles/scroll_hint/NOTES.md.)
+constexpr int kProbeThreads = 256, kProbeWaves = kProbeThreads / 64;
+constexpr int kStripVWords = (16 + 2 * kScrollMaxReach) * 4;
+constexpr int kStripHS4 = kScrollMaxReach / 2 + 5;  // dwords per row of the horizontal strip: 16 + 2D bytes + a group's over-read
+constexpr int kStripHWords = 16 * kStripHS4;
+__global__ __launch_bounds__(kProbeThreads) void k_scroll_probe(Geometry g, StateArg sa,
+                                                                const uint8_t* __restrict__ src_y,
+                                                                uint32_t* __restrict__ hist, int D) {
+    __shared__ uint32_t vs[kStripVWords];
+    __shared__ uint32_t hs[kStripHWords];
+    __shared__ uint32_t srcw[64];
+    __shared__ unsigned long long red[kProbeWaves];
+    __shared__ uint32_t s_flag[1];
+    publish_state(sa);
+    const FrameState& f = state_of(sa);
+    const uint8_t* __restrict__ ref = f.me_ref ? f.me_ref : f.ref_y;
+    const int qp = f.qp;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int npx = scroll_probes_x(g.mb_w);
+    const int x0 = (int)(blockIdx.x % npx) * kScrollLattice * 16, y0 = (int)(blockIdx.x / npx) * kScrollLattice * 16;
+    if (tid < 64) {  // the static exit of the search: one dword of source and reference per lane
+        const int r = tid >> 2, c4 = (tid & 3) * 4;
+        const uint32_t sw = *reinterpret_cast<const uint32_t*>(src_y + (y0 + r) * g.pitch + x0 + c4);
+        const uint32_t rw = *reinterpret_cast<const uint32_t*>(ref + (y0 + r) * g.pitch + x0 + c4);
+        srcw[tid] = sw;
+        const int d = wave_sum((int)__builtin_amdgcn_sad_u8(sw, rw, 0u));
+        if (tid == 0) s_flag[0] = (uint32_t)d;
+    }
+    __syncthreads();
+    if (s_flag[0] > static_sad(qp)) {  // uniform across the workgroup
+        const bool dwords = (g.pitch & 3) == 0 && (reinterpret_cast<uintptr_t>(ref) & 3) == 0;
+        for (int i = tid; i < (16 + 2 * D) * 4; i += kProbeThreads) {  // x0 .. x0 + 15 lies inside the picture
+            const int wy = i >> 2, q = i & 3;
+            const uint8_t* p = ref + (size_t)min(max(y0 - D + wy, 0), g.coded_h - 1) * g.pitch + x0 + 4 * q;
+            vs[i] = dwords ? *reinterpret_cast<const uint32_t*>(p)
+                           : (p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24));
+        }
+        // x0 - D and the coded width are multiples of 4: a dword lies wholly inside a row or beside it
+        const int hw4 = D / 2 + 5;
+        for (int i = tid; i < 16 * hw4; i += kProbeThreads) {
+            const int r = i / hw4, wx4 = i - r * hw4, px = x0 - D + 4 * wx4;
+            const uint8_t* row = ref + (size_t)(y0 + r) * g.pitch;
+            uint32_t w;
+            if (px < 0)
+                w = row[0] * 0x01010101u;
+            else if (px >= g.coded_w)
+                w = row[g.coded_w - 1] * 0x01010101u;
+            else if (dwords)
+                w = *reinterpret_cast<const uint32_t*>(row + px);
+            else
+                w = row[px] | ((uint32_t)row[px + 1] << 8) | ((uint32_t)row[px + 2] << 16) | ((uint32_t)row[px + 3] << 24);
+            hs[r * kStripHS4 + wx4] = w;
+        }
+        __syncthreads();
+        unsigned long long best = ~0ull;
+        for (int c = tid; c <= 2 * D; c += kProbeThreads) {  // vertical: (0, c - D)
+            if (c == D) continue;
+            uint32_t sad = 0;
+#pragma unroll 4
+            for (int r = 0; r < 16; ++r)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) sad = __builtin_amdgcn_sad_u8(srcw[r * 4 + q], vs[(c + r) * 4 + q], sad);
+            const unsigned long long key = scroll_probe_key(sad, 0, c - D, D);
+            best = key < best ? key : best;
+        }
+        {  // horizontal: thread 2 * grp + half scores rows 8 * half .. + 7 of candidates (4 grp + 0..3 - D, 0)
+            const int grp = tid >> 1, half = tid & 1;
+            const bool on = grp <= D / 2;
+            uint64_t acc = 0;  // four shifted SADs, 16 bits each (a 16x16 SAD is <= 65,280)
+            if (on) {
+#pragma unroll 2
+                for (int r = 8 * half; r < 8 * half + 8; ++r) {
+                    const int a = r * kStripHS4 + grp;
+                    const uint32_t w0 = hs[a], w1 = hs[a + 1], w2 = hs[a + 2], w3 = hs[a + 3], w4 = hs[a + 4];
+                    acc = qsad4(w1, w0, srcw[r * 4 + 0], acc);
+                    acc = qsad4(w2, w1, srcw[r * 4 + 1], acc);
+                    acc = qsad4(w3, w2, srcw[r * 4 + 2], acc);
+                    acc = qsad4(w4, w3, srcw[r * 4 + 3], acc);
+                }
+            }
+            acc += __shfl_xor(acc, 1, 64);  // both halves: no field overflows into the next
+            if (on && half == 0) {
+#pragma unroll
+                for (int sh = 0; sh < 4; ++sh) {
+                    const int c = 4 * grp + sh;
+                    if (c > 2 * D || c == D) continue;
+                    const unsigned long long key = scroll_probe_key((uint32_t)(acc >> (16 * sh)) & 0xffffu, 1, c - D, D);
+                    best = key < best ? key : best;
+                }
+            }
+        }
+        for (int o = 32; o > 0; o >>= 1) {
+            const unsigned long long other = __shfl_xor(best, o, 64);
+            best = other < best ? other : best;
+        }
+        if (lane == 0) red[wave] = best;
+        __syncthreads();
+        if (tid == 0) {
+            for (int i = 1; i < kProbeWaves; ++i) best = red[i] < best ? red[i] : best;
+            if (scroll_key_votes(best, qp))
+                __hip_atomic_fetch_add(&hist[scroll_key_bin(best)], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+}
+__global__ __launch_bounds__(kProbeThreads) void k_scroll_decide(int D, uint32_t* __restrict__ hist,
+                                                                 int32_t* __restrict__ hint) {
+    __shared__ unsigned long long red[kProbeWaves];
+    __shared__ uint32_t tot[kProbeWaves];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int nbins = scroll_bins(D);
+    unsigned long long win = 0;
+    uint32_t total = 0;
+    for (int b = tid; b < nbins; b += kProbeThreads) {
+        const uint32_t v = hist[b];
+        if (v) hist[b] = 0u;
+        const unsigned long long key = scroll_bin_key(v, b, D);
+        win = key > win ? key : win;
+        total += v;
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned long long other = __shfl_xor(win, o, 64);
+        win = other > win ? other : win;
+        total += __shfl_xor(total, o, 64);
+    }
+    if (lane == 0) {
+        red[wave] = win;
+        tot[wave] = total;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        for (int i = 1; i < kProbeWaves; ++i) {
+            win = red[i] > win ? red[i] : win;
+            total += tot[i];
+        }
+        int gx, gy;
+        scroll_decide(win, total, D, &gx, &gy);
+        hint[0] = gx;
+        hint[1] = gy;
+    }
 }
 
 // ------------------------------------------------------------------ inter encode
@@ -1221,7 +1436,25 @@ __global__ __launch_bounds__(kMeThreads) __attribute__((amdgpu_waves_per_eu(6)))
     if (blockIdx.x == 0 && threadIdx.x == 0) wave_prog[1] = 0;  // k_intra_analyze's candidate list (next kernel)
     const MeState st = sa.publish ? me_state(sa.v) : me_state(*sa.dst);
     const CodeState cs = sa.publish ? code_state(sa.v) : code_state(*sa.dst);
-    const MbInfo mi = me_full_body(g, st, src_y, mbs, win_lds);  // the same on every thread
+    const MbInfo mi = me_full_body<false>(g, st, src_y, mbs, win_lds);  // the same on every thread
+    __syncthreads();  // every wave is done with the window
+    if (threadIdx.x >= 64) return;
+    inter_code_mb(g, cs, src_y, src_uv, mbs, coef, mb_sse, blockIdx.x, threadIdx.x, mi,
+                  *reinterpret_cast<InterLds*>(win_lds));
+}
+// The same with the scroll hint (after k_scroll_probe, which stamped the start); a kernel of its own,
+// so that k_p_fused keeps its registers
+__global__ __launch_bounds__(kMeThreads) __attribute__((amdgpu_waves_per_eu(6))) void k_p_fused_scroll(
+    Geometry g, StateArg sa, const uint8_t* __restrict__ src_y, const uint8_t* __restrict__ src_uv,
+    MbInfo* __restrict__ mbs, int16_t* __restrict__ coef, uint32_t* __restrict__ mb_sse, int* __restrict__ wave_prog,
+    const int32_t* __restrict__ hint) {
+    __shared__ uint32_t win_lds[kWinWords];
+    static_assert(sizeof(InterLds) <= sizeof(uint32_t) * kWinWords, "the coder's LDS aliases the search window");
+    publish_state(sa);
+    if (blockIdx.x == 0 && threadIdx.x == 0) wave_prog[1] = 0;  // k_intra_analyze's candidate list (next kernel)
+    const MeState st = sa.publish ? me_state(sa.v) : me_state(*sa.dst);
+    const CodeState cs = sa.publish ? code_state(sa.v) : code_state(*sa.dst);
+    const MbInfo mi = me_full_body<true>(g, st, src_y, mbs, win_lds, hint);  // the same on every thread
     __syncthreads();  // every wave is done with the window
     if (threadIdx.x >= 64) return;
     inter_code_mb(g, cs, src_y, src_uv, mbs, coef, mb_sse, blockIdx.x, threadIdx.x, mi,
@@ -2421,7 +2654,8 @@ __global__ __launch_bounds__(kScanThreads) void k_scan_out(Geometry g, const Fra
                                                            uint4* __restrict__ coded_info,
                                                            uint32_t* __restrict__ slice_info, size_t out_bytes,
                                                            OutHeader* __restrict__ hdr,
-                                                           uint32_t* __restrict__ quad_unit, uint32_t* __restrict__ db_cnt) {
+                                                           uint32_t* __restrict__ quad_unit, uint32_t* __restrict__ db_cnt,
+                                                           const int32_t* __restrict__ scroll_hint) {
     __shared__ int s_lbraw[kScanMaxRows + 1];    // last coded MB before row j (any slice), -1 = none
     __shared__ uint32_t s_P[kScanMaxRows + 1];   // unit bits before row j (frame-wide running sum)
     __shared__ uint32_t s_R[kScanMaxRows + 1];   // coded MBs before row j
@@ -2569,6 +2803,9 @@ __global__ __launch_bounds__(kScanThreads) void k_scan_out(Geometry g, const Fra
             hdr->db_changed = db_cnt ? db_cnt[1] : 0u;
             hdr->db_moving = db_cnt ? db_cnt[2] : 0u;
             if (db_cnt) db_cnt[0] = db_cnt[1] = db_cnt[2] = 0;  // re-armed for the slot's next frame
+            const bool hinted = !fs->idr && scroll_hint;  // the hint k_scroll_decide left for this P picture
+            hdr->scroll_dx = (int16_t)(hinted ? scroll_hint[0] : 0);
+            hdr->scroll_dy = (int16_t)(hinted ? scroll_hint[1] : 0);
         }
     }
     // this row's units
@@ -2768,13 +3005,30 @@ void launch_mc_luma_test(const Geometry& g, const uint8_t* ref, int x4, int y4, 
 }
 
 void launch_me(const Geometry& g, const DeviceBuffers& b, const uint8_t* src_y, hipStream_t stream,
-               const FrameState* publish, bool side) {
+               const FrameState* publish, bool side, const ScrollBuffers* scroll) {
     const int nmb = g.mb_w * g.mb_h;
-    const StateArg sa = make_state_arg(b, publish);  // H.264: a P picture's first kernel
+    const StateArg sa = make_state_arg(b, publish, !scroll);  // H.264: a P picture's first kernel, or k_scroll_probe was
+    if (scroll) {
+        if (side && publish)
+            hipLaunchKernelGGL(k_me_full_val_scroll, dim3(nmb), dim3(kMeThreads), 0, stream, g, sa, src_y, b.mb,
+                               scroll->hint);
+        else
+            hipLaunchKernelGGL(k_me_full_scroll, dim3(nmb), dim3(kMeThreads), 0, stream, g, sa, src_y, b.mb,
+                               scroll->hint);
+        return;
+    }
     if (side && publish)
         hipLaunchKernelGGL(k_me_full_val, dim3(nmb), dim3(kMeThreads), 0, stream, g, sa, src_y, b.mb);
     else
         hipLaunchKernelGGL(k_me_full, dim3(nmb), dim3(kMeThreads), 0, stream, g, sa, src_y, b.mb);
+}
+
+void launch_scroll_probe(const Geometry& g, const DeviceBuffers& b, const ScrollBuffers& sb, const uint8_t* src_y,
+                         hipStream_t stream, const FrameState* publish) {
+    const StateArg sa = make_state_arg(b, publish);
+    hipLaunchKernelGGL(k_scroll_probe, dim3(scroll_probes_x(g.mb_w) * scroll_probes_y(g.mb_h)), dim3(kProbeThreads), 0,
+                       stream, g, sa, src_y, sb.hist, sb.reach);
+    hipLaunchKernelGGL(k_scroll_decide, dim3(1), dim3(kProbeThreads), 0, stream, sb.reach, sb.hist, sb.hint);
 }
 
 void launch_inter(const Geometry& g, const DeviceBuffers& b, const uint8_t* src_y, const uint8_t* src_uv,
@@ -2785,11 +3039,15 @@ void launch_inter(const Geometry& g, const DeviceBuffers& b, const uint8_t* src_
 }
 
 void launch_p_fused(const Geometry& g, const DeviceBuffers& b, const uint8_t* src_y, const uint8_t* src_uv,
-                    hipStream_t stream, const FrameState* publish) {
+                    hipStream_t stream, const FrameState* publish, const ScrollBuffers* scroll) {
     const int nmb = g.mb_w * g.mb_h;
-    const StateArg sa = make_state_arg(b, publish);
-    hipLaunchKernelGGL(k_p_fused, dim3(nmb), dim3(kMeThreads), 0, stream, g, sa, src_y, src_uv, b.mb, b.coef, b.mb_sse,
-                       b.wave_prog);
+    const StateArg sa = make_state_arg(b, publish, !scroll);
+    if (scroll)
+        hipLaunchKernelGGL(k_p_fused_scroll, dim3(nmb), dim3(kMeThreads), 0, stream, g, sa, src_y, src_uv, b.mb, b.coef,
+                           b.mb_sse, b.wave_prog, scroll->hint);
+    else
+        hipLaunchKernelGGL(k_p_fused, dim3(nmb), dim3(kMeThreads), 0, stream, g, sa, src_y, src_uv, b.mb, b.coef,
+                           b.mb_sse, b.wave_prog);
 }
 
 static void launch_analyze(const Geometry& g, const DeviceBuffers& b, const uint8_t* src_y, const uint8_t* src_uv,
@@ -2836,7 +3094,7 @@ void launch_save_src(const Geometry& g, const DeviceBuffers& b, const uint8_t* s
 }
 
 void launch_entropy(const Geometry& g, const DeviceBuffers& b, uint8_t* host_out, hipStream_t stream,
-                    hipEvent_t wait_for_sse) {
+                    hipEvent_t wait_for_sse, const int32_t* scroll_hint) {
     const int nmb = g.mb_w * g.mb_h;
     hipLaunchKernelGGL(k_cavlc, dim3((nmb + kCavlcMbPerBlock - 1) / kCavlcMbPerBlock), dim3(256), 0, stream, g, b.fs,
                        b.mb, b.coef, b.slot,
@@ -2847,7 +3105,7 @@ void launch_entropy(const Geometry& g, const DeviceBuffers& b, uint8_t* host_out
     hipLaunchKernelGGL(k_scan_rows, dim3(g.mb_h), dim3(kScanThreads), 0, stream, g, b.fs, b.slot_bits, b.row_agg,
                        b.row_sse, b.mb, b.db_cnt, b.mb_sse);
     hipLaunchKernelGGL(k_scan_out, dim3(g.mb_h), dim3(kScanThreads), 0, stream, g, b.fs, b.slot_bits, b.row_agg,
-                       b.row_sse, b.coded_info, b.slice_info, b.out_bytes, b.out_hdr, b.quad_unit, b.db_cnt);
+                       b.row_sse, b.coded_info, b.slice_info, b.out_bytes, b.out_hdr, b.quad_unit, b.db_cnt, scroll_hint);
     hipLaunchKernelGGL(k_pack, dim3(256), dim3(256), 0, stream, g, b.fs, b.slot, b.coded_info, b.slice_info,
                        b.out_hdr, host_out, b.quad_unit, b.pack_done);
 }

@@ -438,6 +438,64 @@ MXHD uint32_t static_sad(int qp) {
     return t > kStaticSad ? t : kStaticSad;
 }
 
+// ---- scroll hint (EncoderConfig::scroll_range): one axis-aligned displacement per P picture,
+// found by a sparse 1-D probe, on which a macroblock may centre its +-R search instead of on zero.
+// Every rule is here, once, for the probe kernel (k_scroll_probe), the search (me_full_body) and
+// the CPU encoder (scroll_probe_cpu, me_search_cpu): the hint and the vectors stay bit-identical.
+//
+// Largest displacement looked for: [0, 192], rounded up to a multiple of 4 (the probe's strips are
+// staged in whole dwords).  192 + 32 (largest me_range) + 1 (sub-sample refinement) stays inside
+// the vertical vector range [-256, +255.75] of level 3.0, the lowest level pick_level() signals.
+constexpr int kScrollMaxReach = 192;
+MXHD int scroll_reach(int r) {
+    r = r < 0 ? 0 : (r > kScrollMaxReach ? kScrollMaxReach : r);
+    return (r + 3) & ~3;
+}
+// Probe macroblocks: every kScrollLattice-th macroblock in x and in y.
+constexpr int kScrollLattice = 2;
+MXHD bool scroll_is_probe(int mbx, int mby) { return mbx % kScrollLattice == 0 && mby % kScrollLattice == 0; }
+MXHD int scroll_probes_x(int mb_w) { return (mb_w + kScrollLattice - 1) / kScrollLattice; }
+MXHD int scroll_probes_y(int mb_h) { return (mb_h + kScrollLattice - 1) / kScrollLattice; }
+// A hint needs this many probes voting for it, and at least half of all votes cast.
+constexpr uint32_t kScrollMinVotes = 3;
+// Histogram: bins [0, 2D] are the vertical displacements (0, d), bins [2D + 1, 4D + 1] the
+// horizontal ones (d, 0), d = index - D.  The d = 0 bins are never voted for.
+MXHD int scroll_bins(int D) { return 2 * (2 * D + 1); }
+MXHD int scroll_bin(int axis, int d, int D) { return axis * (2 * D + 1) + d + D; }
+// A probe's candidates are ordered by (SAD, |d|, axis (vertical first), index): the smallest key wins.
+MXHD unsigned long long scroll_probe_key(uint32_t sad, int axis, int d, int D) {
+    const uint32_t ad = (uint32_t)(d < 0 ? -d : d);
+    return ((unsigned long long)sad << 32) | (ad << 16) | (uint32_t)scroll_bin(axis, d, D);
+}
+// A probe whose best candidate has key k votes for bin scroll_key_bin(k) when scroll_key_votes(k, qp).
+MXHD bool scroll_key_votes(unsigned long long k, int qp) { return (uint32_t)(k >> 32) <= static_sad(qp); }
+MXHD int scroll_key_bin(unsigned long long k) { return (int)(k & 0xffffu); }
+// The decision over the histogram: most votes, then the smaller |d|, then the vertical axis, then
+// the negative displacement -- the LARGEST bin key wins.  A bin without votes has key 0.
+MXHD unsigned long long scroll_bin_key(uint32_t votes, int bin, int D) {
+    if (!votes) return 0ull;
+    const int axis = bin / (2 * D + 1), d = bin % (2 * D + 1) - D;
+    const uint32_t ad = (uint32_t)(d < 0 ? -d : d);
+    return ((unsigned long long)votes << 32) | ((0xfffu - ad) << 16) | ((uint32_t)(1 - axis) << 15) |
+           ((uint32_t)(d < 0) << 14) | (uint32_t)bin;
+}
+// The hint (full samples) from the winning bin key and the number of votes cast; (0, 0): none.
+MXHD void scroll_decide(unsigned long long best, uint32_t total, int D, int* gx, int* gy) {
+    const uint32_t votes = (uint32_t)(best >> 32);
+    *gx = *gy = 0;
+    if (votes < kScrollMinVotes || 2u * votes < total) return;
+    const int bin = (int)(best & 0x3fffu), axis = bin / (2 * D + 1), d = bin % (2 * D + 1) - D;
+    if (axis) *gx = d; else *gy = d;
+}
+static_assert(2 * (2 * kScrollMaxReach + 1) < (1 << 14), "scroll_bin_key keeps the bin in 14 bits");
+// What a macroblock whose zero vector failed the static exit does with a non-zero hint g:
+// SADg within the static threshold -> it takes vector 4g (16x16) without a search; else the search
+// is centred on g when SADg < SAD0, on zero otherwise.
+enum ScrollUse : int { kScrollExit = 0, kScrollCentre = 1, kScrollZero = 2 };
+MXHD int scroll_use(uint32_t sadg, uint32_t sad0, int qp) {
+    return sadg <= static_sad(qp) ? kScrollExit : (sadg < sad0 ? kScrollCentre : kScrollZero);
+}
+
 // Sub-pel refinement neighbour k (0..7) offsets.
 MXHD void subpel_offset(int k, int* dx, int* dy) {
     *dx = (k < 3) ? (k - 1) : (k == 3 ? -1 : (k == 4 ? 1 : (k - 6)));

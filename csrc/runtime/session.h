@@ -87,6 +87,7 @@ struct FrameResult {
     double psnr_y_masked = 0;                   // luma PSNR outside SessionConfig::mask_* (0 = off)
     int deblocked = 0;                          // H.264: the in-loop filter ran on this picture
     int db_coherent = 0, db_moving = 0;         // H.264: the picture's adaptive-filter classes (h264_deblock.h)
+    int scroll_dx = 0, scroll_dy = 0;           // H.264: the scroll hint used for this picture (EncoderConfig::scroll_range)
     std::vector<uint8_t> au;
 };
 

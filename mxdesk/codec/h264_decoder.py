@@ -923,6 +923,19 @@ class Decoder:
             self._ref_key = self.ref
         return self._refp
 
+    @staticmethod
+    def _window(R, y, x, h, w):
+        """Rows y .. y+h-1, columns x .. x+w-1 of the edge-padded plane R.  A window inside the
+        padding is a slice; one that leaves it (a vector pointing further outside the picture than
+        PAD) takes its samples at clamped coordinates -- the padding repeats the edge sample, so
+        both give the edge-extended reference of 8.4.2.2."""
+        H, W = R.shape
+        if y >= 0 and x >= 0 and y + h <= H and x + w <= W:
+            return R[y: y + h, x: x + w]
+        rows = np.clip(np.arange(y, y + h), 0, H - 1)
+        cols = np.clip(np.arange(x, x + w), 0, W - 1)
+        return R[rows[:, None], cols[None, :]]
+
     def pred_luma_inter(self, x0, y0, w, h, mvx, mvy) -> np.ndarray:
         P = self.PAD
         R = self._ref_padded()[0]
@@ -930,7 +943,7 @@ class Decoder:
         xf, yf = mvx & 3, mvy & 3
 
         def G(dx, dy, ww=w, hh=h):
-            return R[yi + dy: yi + dy + hh, xi + dx: xi + dx + ww]
+            return self._window(R, yi + dy, xi + dx, hh, ww)
 
         def b1_at(dy):  # horizontal half intermediate at rows yi+dy.., cols xi..
             return _tap6(G(-2, dy), G(-1, dy), G(0, dy), G(1, dy), G(2, dy), G(3, dy))
@@ -975,10 +988,10 @@ class Decoder:
         R = self._ref_padded()[1 + comp]
         xi, yi = xc0 + (mvx >> 3) + P, yc0 + (mvy >> 3) + P
         xf, yf = mvx & 7, mvy & 7
-        A = R[yi: yi + h, xi: xi + w]
-        B = R[yi: yi + h, xi + 1: xi + 1 + w]
-        C = R[yi + 1: yi + 1 + h, xi: xi + w]
-        D = R[yi + 1: yi + 1 + h, xi + 1: xi + 1 + w]
+        A = self._window(R, yi, xi, h, w)
+        B = self._window(R, yi, xi + 1, h, w)
+        C = self._window(R, yi + 1, xi, h, w)
+        D = self._window(R, yi + 1, xi + 1, h, w)
         return ((8 - xf) * (8 - yf) * A + xf * (8 - yf) * B + (8 - xf) * yf * C + xf * yf * D + 32) >> 6
 
     # ------------------------------------------------------------------ motion vectors

@@ -205,7 +205,7 @@ class StreamPipeline:
                  noise: bool = True, out_width: int = 0, out_height: int = 0, session_name: str = "0",
                  capture: Any = None, metrics: SessionMetrics | None = None, queue_frames: int | None = None,
                  stall_s: float = 2.0, paced: bool = True, codec: str = "h264",
-                 idr_min_interval_s: float | None = None):
+                 idr_min_interval_s: float | None = None, scroll_range: int = 0):
         if codec not in CODEC_IDS:
             raise ValueError(f"unknown codec {codec!r} (h264 | hevc | vp8)")
         self.codec = codec
@@ -224,7 +224,8 @@ class StreamPipeline:
         self.paced = paced
         self.bitrate_kbps = bitrate_kbps  # configured CBR target (congestion control upper bound)
         self._enc_args = dict(bitrate_kbps=bitrate_kbps, keyint=keyint, search_range=search_range, subpel=subpel,
-                              noise=noise)
+                              noise=noise, scroll_range=scroll_range)
+        self.last_scroll = (0, 0)  # scroll hint of the last P picture (H.264 with scroll_range; /status)
         self._subs: list[_Subscriber] = []
         self._lock = threading.Lock()
         self._stop = threading.Event()
@@ -274,6 +275,7 @@ class StreamPipeline:
             cfg.enc.bitrate_kbps = a["bitrate_kbps"]
             cfg.enc.keyint = a["keyint"]
             cfg.enc.search_range = a["search_range"]
+            cfg.enc.scroll_range = a["scroll_range"]
             cfg.enc.subpel = 1 if a["subpel"] else 0
             cfg.codec = self.codec
             self._sess = N.Session(cfg)
@@ -362,6 +364,7 @@ class StreamPipeline:
                 r = s.collect()
             else:
                 r = s.step(force_idr)
+            self.last_scroll = (r.scroll_dx, r.scroll_dy)
             return EncodedFrame(r.frame_id, r.t_capture_us, r.t_encoded_us, bool(r.idr), r.qp, r.au, self.out_w,
                                 self.out_h, r.gpu_ms, self.codec_id)
         t_cap = native().now_us()
@@ -540,7 +543,7 @@ class StreamPipeline:
         return {"backend": self.backend, "device": self.device, "width": self.out_w, "height": self.out_h,
                 "fps": self.fps, "frames": self.frames_out, "clients": self.subscribers, "restarts": self.restarts,
                 "last_error": self.last_error, "resizes": self.resizes, "keyframes": self.keyframes.snapshot(),
-                "frames_idle": self.frames_idle,
+                "frames_idle": self.frames_idle, "scroll_hint": list(self.last_scroll),
                 **self.metrics.summary()}
 
 

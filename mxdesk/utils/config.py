@@ -151,6 +151,8 @@ SCHEMA: list[Var] = [
     Var("out_width", ["MXDESK_OUT_WIDTH"], 0, int, "encoded width (0 = SIZEW; else Lanczos scale)"),
     Var("out_height", ["MXDESK_OUT_HEIGHT"], 0, int, "encoded height (0 = SIZEH)"),
     Var("search_range", ["MXDESK_SEARCH_RANGE"], 16, int, "motion search radius (integer pels, <= 32)"),
+    Var("scroll_range", ["MXDESK_SCROLL_RANGE"], 0, int,
+        "H.264: largest scroll (luma samples, <= 192) the P-picture probe pass looks for; 0 = off"),
     Var("subpel", ["MXDESK_SUBPEL"], True, bool, "quarter-pel motion refinement"),
     Var("noise", ["MXDESK_NOISE"], True, bool, "synthetic desktop: animated-noise panel"),
     Var("wall", ["MXDESK_WALL"], "", str, "tiled wall layout, e.g. '2x2' (one tile per GPU)"),
@@ -259,6 +261,8 @@ class Config:
             raise ValueError("TURN_PROTOCOL must be udp or tcp")
         if not 1 <= v["search_range"] <= 32:
             raise ValueError("MXDESK_SEARCH_RANGE must be in [1, 32]")
+        if not 0 <= v["scroll_range"] <= 192:
+            raise ValueError("MXDESK_SCROLL_RANGE must be in [0, 192]")
         if v["source"] not in ("auto", "synthetic", "x11"):
             raise ValueError("MXDESK_SOURCE must be auto, synthetic or x11")
         self.encoder_backend  # noqa: B018  (raises on unknown encoders)
