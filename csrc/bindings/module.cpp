@@ -660,13 +660,15 @@ PYBIND11_MODULE(_native, m) {
                 pix::upload_scale_frags(fr, &frags, t.mf);
                 t.mf.force_strip = strip;  // else the one-tile-per-workgroup MFMA kernel
             }
-            pix::launch_scale_to_nv12(as_ptr<const uint8_t>(in), in_pitch, in_w, in_h, t, as_ptr<uint8_t>(y),
-                                      as_ptr<uint8_t>(uv), out_pitch, cw, ch, as_stream(stream));
+            const pix::ScaleForm form =
+                pix::launch_scale_to_nv12(as_ptr<const uint8_t>(in), in_pitch, in_w, in_h, t, as_ptr<uint8_t>(y),
+                                          as_ptr<uint8_t>(uv), out_pitch, cw, ch, as_stream(stream));
             HIP_CHECK(hipGetLastError());
             if (frags) {
                 HIP_CHECK(hipStreamSynchronize(as_stream(stream)));
                 HIP_CHECK(hipFree(frags));
             }
+            return std::string(pix::scale_form_name(form));  // "valu", "tile" or "strip": the kernel that ran
         },
         py::arg("in_ptr"), py::arg("in_pitch"), py::arg("in_w"), py::arg("in_h"), py::arg("out_w"), py::arg("out_h"),
         py::arg("x0_ptr"), py::arg("wx_ptr"), py::arg("taps_x"), py::arg("y0_ptr"), py::arg("wy_ptr"),
@@ -693,6 +695,70 @@ PYBIND11_MODULE(_native, m) {
         std::memcpy(wa.mutable_data(), w.data(), w.size() * 4);
         return py::make_tuple(sa, wa, taps);
     });
+    m.def(
+        "scale_plan",
+        [](int in_w, int in_h, int out_w, int out_h) {
+            // host only: which scaler kernel and instantiation a geometry selects (coded size = the
+            // output rounded up to 16, as the encoders')
+            if (in_w < 1 || in_h < 1 || out_w < 1 || out_h < 1) throw std::invalid_argument("scale_plan: bad geometry");
+            std::vector<int> sx, sy;
+            std::vector<float> wx, wy;
+            int tx, ty;
+            make_lanczos_table(in_w, out_w, sx, wx, tx);
+            make_lanczos_table(in_h, out_h, sy, wy, ty);
+            const int cw = (out_w + 15) / 16 * 16, ch = (out_h + 15) / 16 * 16;
+            pix::ScaleFragsHost fr;
+            const bool ok = pix::build_scale_frags(in_w, in_h, out_w, out_h, cw, ch, sx, wx, tx, sy, wy, ty, fr);
+            py::dict d;
+            d["taps_x"] = tx;
+            d["taps_y"] = ty;
+            d["mfma"] = ok;
+            d["nk"] = ok ? fr.nk : 0;
+            d["nrb_max"] = ok ? fr.nrb_max : 0;
+            d["strip"] = ok ? fr.strip : 0;
+            d["lds_cols"] = ok ? fr.lds_cols : 0;
+            d["valu_lds_bytes"] = pix::scale_valu_lds_bytes(in_w, in_h, out_w, out_h, tx, ty);
+            return d;
+        },
+        py::arg("in_w"), py::arg("in_h"), py::arg("out_w"), py::arg("out_h"));
+    m.def(
+        "sse_masked",
+        [](uintptr_t a, uintptr_t b, int pitch, int w, int h, int mx0, int my0, int mx1, int my1, int repeat,
+           uintptr_t stream) {
+            // k_sse_masked with scratch allocated as Session does (partials, a counter zeroed once,
+            // a mapped host word), launched `repeat` times on the same scratch: one total per launch
+            if (w < 1 || h < 1 || repeat < 1) throw std::invalid_argument("sse_masked: bad geometry");
+            unsigned long long* part = nullptr;
+            unsigned int* counter = nullptr;
+            unsigned long long* host = nullptr;
+            std::vector<unsigned long long> totals;
+            auto release = [&] {
+                if (part) (void)hipFree(part);
+                if (counter) (void)hipFree(counter);
+                if (host) (void)hipHostFree(host);
+            };
+            try {
+                HIP_CHECK(hipMalloc(&part, (size_t)pix::sse_masked_blocks(w, h) * sizeof(unsigned long long)));
+                HIP_CHECK(hipMalloc(&counter, sizeof(unsigned int)));
+                HIP_CHECK(hipMemset(counter, 0, sizeof(unsigned int)));
+                HIP_CHECK(hipHostMalloc(&host, sizeof(unsigned long long), hipHostMallocMapped));
+                for (int i = 0; i < repeat; ++i) {
+                    *host = ~0ull;
+                    pix::launch_sse_masked(as_ptr<const uint8_t>(a), as_ptr<const uint8_t>(b), pitch, w, h, mx0, my0,
+                                           mx1, my1, part, counter, host, as_stream(stream));
+                    HIP_CHECK(hipGetLastError());
+                    HIP_CHECK(hipStreamSynchronize(as_stream(stream)));
+                    totals.push_back(*host);
+                }
+            } catch (...) {
+                release();
+                throw;
+            }
+            release();
+            return totals;
+        },
+        py::arg("a_ptr"), py::arg("b_ptr"), py::arg("pitch"), py::arg("width"), py::arg("height"), py::arg("mx0"),
+        py::arg("my0"), py::arg("mx1"), py::arg("my1"), py::arg("repeat") = 1, py::arg("stream") = 0);
     m.attr("BARCODE_CELL") = pix::kBarCell;
     m.attr("BARCODE_X") = pix::kBarX;
     m.attr("BARCODE_Y") = pix::kBarY;

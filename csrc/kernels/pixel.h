@@ -94,9 +94,17 @@ bool build_scale_frags(int in_w, int in_h, int out_w, int out_h, int coded_w, in
                        const std::vector<float>& wy, int ty, ScaleFragsHost& out);
 // Copies the blob to `dev` (hipMalloc'ed here; caller frees) and fills `mf`.
 void upload_scale_frags(const ScaleFragsHost& h, void** dev, ScaleMfma& mf);
-void launch_scale_to_nv12(const uint8_t* bgrx, int in_pitch, int in_w, int in_h, const LanczosTables& t, uint8_t* y,
-                          uint8_t* uv, int out_pitch, int coded_w, int coded_h, hipStream_t stream,
-                          uint64_t* ts = nullptr);
+// LDS bytes of one VALU-kernel tile (k_scale_to_nv12) for this geometry, and the footprint it is
+// sized for: max_nc staged columns (whole quads) x max_nr rows.
+size_t scale_valu_lds_bytes(int in_w, int in_h, int out_w, int out_h, int taps_x, int taps_y, int* max_nc = nullptr,
+                            int* max_nr = nullptr);
+// The form of the scaler a launch ran: the VALU kernel, the matrix-core kernel with one tile per
+// workgroup, or its strip form.
+enum class ScaleForm { kValu, kTile, kStrip };
+const char* scale_form_name(ScaleForm f);
+ScaleForm launch_scale_to_nv12(const uint8_t* bgrx, int in_pitch, int in_w, int in_h, const LanczosTables& t,
+                               uint8_t* y, uint8_t* uv, int out_pitch, int coded_w, int coded_h, hipStream_t stream,
+                               uint64_t* ts = nullptr);
 
 // Luma squared error between two planes over [0,w) x [0,h) excluding the rectangle
 // [mx0,mx1) x [my0,my1) (quality report with a panel masked out), in one dispatch: `part`

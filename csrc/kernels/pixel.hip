@@ -1467,8 +1467,26 @@ void upload_scale_frags(const ScaleFragsHost& h, void** dev, ScaleMfma& mf) {
     mf.strip = h.strip;
 }
 
-void launch_scale_to_nv12(const uint8_t* bgrx, int in_pitch, int in_w, int in_h, const LanczosTables& t, uint8_t* y,
-                          uint8_t* uv, int out_pitch, int coded_w, int coded_h, hipStream_t stream, uint64_t* ts) {
+size_t scale_valu_lds_bytes(int in_w, int in_h, int out_w, int out_h, int taps_x, int taps_y, int* max_nc_out,
+                            int* max_nr_out) {
+    // worst-case footprint of a tile: scale * tile + taps
+    const float sx = (float)in_w / out_w, sy = (float)in_h / out_h;
+    // +4 columns for the aligned start, rounded to whole quads (16-byte LDS stores)
+    const int max_nc = (((int)ceilf(sx * kTileW) + taps_x + 2 + 4) + 3) & ~3;
+    const int max_nr = (int)ceilf(sy * kTileH) + taps_y + 2;
+    if (max_nc_out) *max_nc_out = max_nc;
+    if (max_nr_out) *max_nr_out = max_nr;
+    return (((size_t)max_nr * max_nc * 4 + 15) & ~(size_t)15) + ((3 * (size_t)max_nr * kTileW + 7) & ~(size_t)7) * 2 +
+           (size_t)(kTileW * taps_x + kTileH * taps_y) * 4 + (kTileW + kTileH) * 4;
+}
+
+const char* scale_form_name(ScaleForm f) {
+    return f == ScaleForm::kValu ? "valu" : f == ScaleForm::kTile ? "tile" : "strip";
+}
+
+ScaleForm launch_scale_to_nv12(const uint8_t* bgrx, int in_pitch, int in_w, int in_h, const LanczosTables& t,
+                               uint8_t* y, uint8_t* uv, int out_pitch, int coded_w, int coded_h, hipStream_t stream,
+                               uint64_t* ts) {
     // the strip form runs only on request (MXDESK_SCALER=strip, or the binding's strip=True): with
     // one 2-wave workgroup per CU it leaves half the SIMDs idle and measured 80 us against the tile
     // kernel's 26 us for 4K -> 1080p (profiles/r05_scale/NOTES.md)
@@ -1484,7 +1502,7 @@ void launch_scale_to_nv12(const uint8_t* bgrx, int in_pitch, int in_w, int in_h,
         dim3 grid((coded_w + 63) / 64, (t.mf.ngy + t.mf.strip - 1) / t.mf.strip);
         hipLaunchKernelGGL(k_scale_strip, grid, dim3(128), lds, stream, bgrx, in_pitch, in_w, in_h, t.mf, y, uv,
                            out_pitch, coded_w, coded_h, ts);
-        return;
+        return ScaleForm::kStrip;
     }
     if (t.mf.gx && t.mf.ngx == (coded_w + 31) / 32 && t.mf.ngy == (coded_h + 31) / 32 && in_w >= 4) {
         const size_t lds = (size_t)2 * 32 * t.mf.lds_cols * 4;
@@ -1512,16 +1530,10 @@ void launch_scale_to_nv12(const uint8_t* bgrx, int in_pitch, int in_w, int in_h,
             by_nk(std::integral_constant<int, 3>{});
         else
             by_nk(std::integral_constant<int, kMfRb>{});
-        return;
+        return ScaleForm::kTile;
     }
-    // worst-case footprint of a tile: scale * tile + taps
-    const float sx = (float)in_w / t.out_w, sy = (float)in_h / t.out_h;
-    // +4 columns for the aligned start, rounded to whole quads (16-byte LDS stores)
-    const int max_nc = (((int)ceilf(sx * kTileW) + t.taps_x + 2 + 4) + 3) & ~3;
-    const int max_nr = (int)ceilf(sy * kTileH) + t.taps_y + 2;
-    const size_t lds = (((size_t)max_nr * max_nc * 4 + 15) & ~(size_t)15) +
-                       ((3 * (size_t)max_nr * kTileW + 7) & ~(size_t)7) * 2 +
-                       (size_t)(kTileW * t.taps_x + kTileH * t.taps_y) * 4 + (kTileW + kTileH) * 4;
+    int max_nc, max_nr;
+    const size_t lds = scale_valu_lds_bytes(in_w, in_h, t.out_w, t.out_h, t.taps_x, t.taps_y, &max_nc, &max_nr);
     const int vec = ((in_pitch & 15) == 0 && (reinterpret_cast<uintptr_t>(bgrx) & 15) == 0) ? 1 : 0;
     if (lds > 160 * 1024) throw std::runtime_error("scale_to_nv12: scale factor too large for one LDS tile");
     if (lds > 64 * 1024) {
@@ -1531,6 +1543,7 @@ void launch_scale_to_nv12(const uint8_t* bgrx, int in_pitch, int in_w, int in_h,
     dim3 grid((coded_w + kTileW - 1) / kTileW, (coded_h + kTileH - 1) / kTileH);
     hipLaunchKernelGGL(k_scale_to_nv12, grid, dim3(256), lds, stream, bgrx, in_pitch, in_w, in_h, t, y, uv, out_pitch,
                        coded_w, coded_h, max_nc, max_nr, vec, ts);
+    return ScaleForm::kValu;
 }
 
 void launch_composite(const uint8_t* tile, int tile_pitch, int tw, int th, uint8_t* dst, int dst_pitch, int dx, int dy,
