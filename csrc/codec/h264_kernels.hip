@@ -260,6 +260,142 @@ struct MeState {
 __device__ __forceinline__ MeState me_state(const FrameState& f) {
     return MeState{f.me_ref ? f.me_ref : f.ref_y, f.qp, f.search_range, f.subpel, f.me_coarse, f.partitions};
 }
+// The 16x16 SAD of the zero vector (the static exit), one wave calling (tid < 64): a dword of source
+// and of reference per lane, v_sad_u8, summed over the wave.  *sw: this lane's source dword.
+__device__ __forceinline__ uint32_t zero_sad_wave(const uint8_t* __restrict__ src_y, const uint8_t* __restrict__ ref,
+                                                  int pitch, int x0, int y0, int tid, uint32_t* sw) {
+    const int r = tid >> 2, c4 = (tid & 3) * 4;
+    *sw = *reinterpret_cast<const uint32_t*>(src_y + (y0 + r) * pitch + x0 + c4);
+    const uint32_t rw = *reinterpret_cast<const uint32_t*>(ref + (y0 + r) * pitch + x0 + c4);
+    return (uint32_t)wave_sum((int)__builtin_amdgcn_sad_u8(*sw, rw, 0u));
+}
+__device__ __forceinline__ unsigned long long kmin(unsigned long long a, unsigned long long c) { return c < a ? c : a; }
+// The minimum of the kMeWaves per-wave keys a block reduction left in LDS.
+__device__ __forceinline__ unsigned long long block_min(const unsigned long long* slot) {
+    unsigned long long b = slot[0];
+    for (int i = 1; i < kMeWaves; ++i) b = kmin(b, slot[i]);
+    return b;
+}
+// Row r of a scoring task: the five window dwords at win32[a] (a dword-aligned 20-byte span shared by
+// the four horizontally adjacent candidates) against the four source dwords of the row.  The left
+// and right halves of the row go to lft and rgt: a quadrant pair, or one 16x16 accumulator twice.
+__device__ __forceinline__ void me_row(const uint32_t* win32, const uint32_t* srcw, int a, int r, uint64_t& lft,
+                                       uint64_t& rgt) {
+    const uint32_t w0 = win32[a], w1 = win32[a + 1], w2 = win32[a + 2], w3 = win32[a + 3], w4 = win32[a + 4];
+    const uint32_t s0 = srcw[r * 4 + 0], s1 = srcw[r * 4 + 1], s2 = srcw[r * 4 + 2], s3 = srcw[r * 4 + 3];
+    lft = qsad4(w1, w0, s0, lft);
+    lft = qsad4(w2, w1, s1, lft);
+    rgt = qsad4(w3, w2, s2, rgt);
+    rgt = qsad4(w4, w3, s3, rgt);
+}
+// The 16x16 scoring loop.  Task q is dword group q % gw of candidate row q / gw; kCoarse takes every
+// second row and shifts 0 and 2 of the group (the even-offset grid), otherwise every row and all four
+// shifts.  visit(sad, dxr, dyr) gets each candidate inside the window.
+template <bool kCoarse, class Visit>
+__device__ __forceinline__ void me_score16(const uint32_t* win32, const uint32_t* srcw, int ntask, int gw, int side,
+                                           int tid, Visit visit) {
+    constexpr int kStep = kCoarse ? 2 : 1, kUnroll = kCoarse ? 4 : 2;
+    for (int q = tid; q < ntask; q += kMeThreads) {
+        const int dyr = kStep * (q / gw), g = q % gw;
+        uint64_t acc = 0;  // four shifted 16x16 SADs, 16 bits each (<= 65,280)
+#pragma unroll kUnroll
+        for (int r = 0; r < 16; ++r) me_row(win32, srcw, (dyr + r) * (kWinStride / 4) + g, r, acc, acc);
+#pragma unroll
+        for (int sh = 0; sh < 4; sh += kStep) {
+            const int dxr = 4 * g + sh;
+            if (dxr >= side) break;
+            visit((uint32_t)(acc >> (16 * sh)) & 0xffffu, dxr, dyr);
+        }
+    }
+}
+// One of the 8 integer neighbours (subpel_offset order k) of the grid best `centre`, scored by a
+// group of kLanes adjacent lanes: sad(nxr, nyr) is this lane's share of the SAD at window position
+// (nxr, nyr).  Returns the neighbour's key on every lane of the group, ~0 when it lies outside the
+// window (uniform per group).
+template <int kLanes, class Sad, class Key>
+__device__ __forceinline__ unsigned long long me_neighbour(unsigned long long centre, int k, int side, Sad sad,
+                                                           Key mkey) {
+    const int cb0 = (int)(centre & 0xffff), bxr = cb0 % side, byr = cb0 / side;
+    int ddx, ddy;
+    subpel_offset(k, &ddx, &ddy);
+    const int nxr = bxr + ddx, nyr = byr + ddy;
+    const bool inside = nxr >= 0 && nxr < side && nyr >= 0 && nyr < side;
+    int d = inside ? sad(nxr, nyr) : 0;
+    for (int o = kLanes / 2; o > 0; o >>= 1) d += __shfl_xor(d, o, 64);
+    return inside ? mkey((uint32_t)d, nxr, nyr) : ~0ull;
+}
+// Half- then quarter-sample refinement of kN vectors (vx, vy, cost) at once, the whole workgroup
+// calling.  The 8 candidates of a step around vector pi are scored by groups of 256 / (8 kN) lanes;
+// this lane is lane `sub` of candidate k of vector pi and owns the 8 source samples at (xx, yy) of
+// the macroblock (srcw).  sp[pi]: the footprint staged around the integer match (vx, vy)[pi] on entry.
+// A step publishes its costs in cand (two barriers) and every thread takes the first lower cost in
+// subpel_offset order.
+template <int kN>
+__device__ __forceinline__ void me_refine(const uint8_t (*sp)[4][18][kSpW], uint32_t (*cand)[8], const uint32_t* srcw,
+                                          int pi, int k, int sub, int xx, int yy, int lambda, int* vx, int* vy,
+                                          uint32_t* cost) {
+    const uint32_t s0 = srcw[yy * 4 + (xx >> 2)], s1 = srcw[yy * 4 + (xx >> 2) + 1];
+    const int base_x4 = xx * 4 + 4 - vx[pi], base_y4 = yy * 4 + 4 - vy[pi];  // local qpel coords = base + candidate mv
+    for (int step = 2; step >= 1; step >>= 1) {
+        int ddx, ddy;
+        subpel_offset(k, &ddx, &ddy);
+        const int cx = vx[pi] + ddx * step, cy = vy[pi] + ddy * step;
+        int d = 0;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            d += abs(byte_of(j < 4 ? s0 : s1, j & 3) - qpel_lds(sp[pi], base_x4 + 4 * j + cx, base_y4 + cy));
+        }
+        for (int o = kMeThreads / (16 * kN); o > 0; o >>= 1) d += __shfl_xor(d, o, 64);
+        __syncthreads();  // the previous step's readers are done with cand
+        if (sub == 0) cand[pi][k] = me_cost((uint32_t)d, lambda, cx, cy);
+        __syncthreads();
+        for (int q = 0; q < kN; ++q) {
+            int bdx = 0, bdy = 0;
+            uint32_t bcost = cost[q];
+            for (int kk = 0; kk < 8; ++kk) {
+                const uint32_t cc = cand[q][kk];
+                if (cc < bcost) {
+                    int ex, ey;
+                    subpel_offset(kk, &ex, &ey);
+                    bcost = cc;
+                    bdx = ex * step;
+                    bdy = ey * step;
+                }
+            }
+            vx[q] += bdx;
+            vy[q] += bdy;
+            cost[q] = bcost;
+        }
+    }
+}
+// Thread 0 stores the macroblock's motion in mbs[mbi]; every thread gets it back.  The vectors are
+// local to the search centre (cx, cy; full samples), which is added here.  pvx / pvy: the two
+// partition vectors of a 16x8 / 8x16 macroblock (a 16x16 one stores zeros).
+__device__ __forceinline__ MbInfo store_motion(MbInfo* __restrict__ mbs, int mbi, int tid, int cx, int cy, int mvx,
+                                               int mvy, int part, const int (&pvx)[2], const int (&pvy)[2]) {
+    MbInfo out;
+    out.mvx = (int16_t)(4 * cx + mvx);
+    out.mvy = (int16_t)(4 * cy + mvy);
+    out.part = (uint8_t)part;
+    for (int i = 0; i < 2; ++i) {
+        out.pmv[2 * i] = part == kPart16x16 ? 0 : (int16_t)(4 * cx + pvx[i]);
+        out.pmv[2 * i + 1] = part == kPart16x16 ? 0 : (int16_t)(4 * cy + pvy[i]);
+    }
+    if (tid == 0) {
+        MbInfo& m = mbs[mbi];
+        m.mvx = out.mvx;
+        m.mvy = out.mvy;
+        m.part = out.part;
+        for (int i = 0; i < 4; ++i) m.pmv[i] = out.pmv[i];
+    }
+    return out;
+}
+// The same for a 16x16 macroblock.
+__device__ __forceinline__ MbInfo store_motion(MbInfo* __restrict__ mbs, int mbi, int tid, int cx, int cy, int mvx,
+                                               int mvy) {
+    const int none[2] = {0, 0};
+    return store_motion(mbs, mbi, tid, cx, cy, mvx, mvy, kPart16x16, none, none);
+}
 // Returns the motion it stored in mbs[mbi] (mvx, mvy, part, pmv; the same on every thread): the
 // fused kernel codes the macroblock from it without reading it back.  win_lds: kWinWords of LDS.
 // kScroll (H.264 with EncoderConfig::scroll_range): a macroblock that fails the static exit looks at
@@ -271,10 +407,7 @@ template <bool kScroll>
 __device__ __forceinline__ MbInfo me_full_body(const Geometry& g, const MeState& st, const uint8_t* __restrict__ src_y,
                                                MbInfo* __restrict__ mbs, uint32_t* win_lds,
                                                const int32_t* __restrict__ hint = nullptr) {
-    MbInfo out;
-    out.mvx = out.mvy = 0;
-    out.part = kPart16x16;
-    out.pmv[0] = out.pmv[1] = out.pmv[2] = out.pmv[3] = 0;
+    static_assert(kMeThreads == 256, "the neighbour and refinement layouts: 8 candidates x 32 lanes");
     __shared__ uint8_t sp2[2][4][18][kSpW];   // sub-sample footprints: the 16x16 match, or two partitions
     __shared__ int16_t fp_b1[2][kFpRows][kSpW];
     __shared__ uint32_t srcw[64];
@@ -298,16 +431,20 @@ __device__ __forceinline__ MbInfo me_full_body(const Geometry& g, const MeState&
     constexpr int kWs4 = kWinStride / 4;
     int cx = 0, cy = 0;  // the centre of the search, full samples
     {
-        if (tid < 64) {  // one wave: a dword of source and reference per lane, v_sad_u8
-            const int r = tid >> 2, c4 = (tid & 3) * 4;
-            const uint32_t sw = *reinterpret_cast<const uint32_t*>(src_y + (y0 + r) * g.pitch + x0 + c4);
-            const uint32_t rw = *reinterpret_cast<const uint32_t*>(ref + (y0 + r) * g.pitch + x0 + c4);
-            const int d = wave_sum((int)__builtin_amdgcn_sad_u8(sw, rw, 0u));
-            if (tid == 0) s_sad0[0] = (uint32_t)d;
+        if (tid < 64) {
+            uint32_t sw;
+            const uint32_t d = zero_sad_wave(src_y, ref, g.pitch, x0, y0, tid, &sw);
+            if (tid == 0) s_sad0[0] = d;
         }
         __syncthreads();
         const uint32_t sad0 = s_sad0[0];
-        if (sad0 <= static_sad(st.qp)) {
+        if (sad0 <= static_sad(st.qp)) {  // uniform across the workgroup
+            // written out: through store_motion the compiler merges this store with the search's last
+            // one, and k_me_full and k_me_full_val need two more SGPRs (profiles/search_once)
+            MbInfo out;
+            out.mvx = out.mvy = 0;
+            out.part = kPart16x16;
+            out.pmv[0] = out.pmv[1] = out.pmv[2] = out.pmv[3] = 0;
             if (tid == 0) {
                 MbInfo& m = mbs[mbi];
                 m.mvx = 0;
@@ -315,7 +452,7 @@ __device__ __forceinline__ MbInfo me_full_body(const Geometry& g, const MeState&
                 m.part = kPart16x16;
                 m.pmv[0] = m.pmv[1] = m.pmv[2] = m.pmv[3] = 0;
             }
-            return out;  // uniform across the workgroup
+            return out;
         }
         if constexpr (kScroll) {
             const int gx = hint[0], gy = hint[1];  // uniform (k_scroll_decide's, the kernel before)
@@ -331,18 +468,7 @@ __device__ __forceinline__ MbInfo me_full_body(const Geometry& g, const MeState&
                 }
                 __syncthreads();
                 const int use = scroll_use(s_sad0[1], sad0, st.qp);
-                if (use == kScrollExit) {
-                    if (tid == 0) {
-                        MbInfo& m = mbs[mbi];
-                        m.mvx = (int16_t)(4 * gx);
-                        m.mvy = (int16_t)(4 * gy);
-                        m.part = kPart16x16;
-                        m.pmv[0] = m.pmv[1] = m.pmv[2] = m.pmv[3] = 0;
-                    }
-                    out.mvx = (int16_t)(4 * gx);
-                    out.mvy = (int16_t)(4 * gy);
-                    return out;  // uniform
-                }
+                if (use == kScrollExit) return store_motion(mbs, mbi, tid, gx, gy, 0, 0);  // uniform
                 if (use == kScrollCentre) cx = gx, cy = gy;
             }
         }
@@ -350,7 +476,6 @@ __device__ __forceinline__ MbInfo me_full_body(const Geometry& g, const MeState&
     // search window straight from the reference picture, edge-clamped.  Its left edge x0 - R - 4 is
     // a multiple of 4 and so is the coded width: a window dword lies wholly inside a picture row
     // (one dword load) or wholly beside it (the row's edge sample four times) -- no byte gathers.
-    const bool t256 = tid < 256;  // the threads of the 256-thread refinement layouts
     const int wrows = W + 2 * kWinPadY + 1, wx0 = x0 + cx - R - kWinPadX, wy0 = y0 + cy - R - kWinPadY;
     const bool dwords = (g.pitch & 3) == 0 && (reinterpret_cast<uintptr_t>(ref) & 3) == 0;
     for (int i = tid; i < wrows * kWs4; i += kMeThreads) {
@@ -395,7 +520,6 @@ __device__ __forceinline__ MbInfo me_full_body(const Geometry& g, const MeState&
     // shifts 0 and 2 of a dword group), (R + 1) * gw tasks in one pass -- then the 8 integer
     // neighbours of its best (me_search_cpu does the same)
     const bool parts = st.partitions != 0;  // 16x8 / 8x16 partitionings searched too (me_search_parts_cpu)
-    const int ntask = (coarse && !parts) ? (R + 1) * gw : 0;
     auto mkey = [&](uint32_t sad, int dxr, int dyr) {
         const int dx = dxr - R, dy = dyr - R;
         const uint32_t cost = me_cost(sad, lambda, 4 * dx, 4 * dy);
@@ -405,7 +529,6 @@ __device__ __forceinline__ MbInfo me_full_body(const Geometry& g, const MeState&
     // partitions: per candidate the SAD of each 8x8 quadrant (TL, TR, BL, BR); the 16x16 key is
     // their sum (so the 16x16 decision is unchanged) and shapes T / B / L / R keep their own best
     unsigned long long pb[4] = {~0ull, ~0ull, ~0ull, ~0ull};
-    auto kmin = [](unsigned long long a, unsigned long long c) { return c < a ? c : a; };
     auto visit_quads = [&](const uint32_t* qd, int dxr, int dyr) {
         best = kmin(best, mkey(qd[0] + qd[1] + qd[2] + qd[3], dxr, dyr));
         pb[0] = kmin(pb[0], mkey(qd[0] + qd[1], dxr, dyr));
@@ -421,24 +544,11 @@ __device__ __forceinline__ MbInfo me_full_body(const Geometry& g, const MeState&
             // one packed accumulator per quadrant: the four shifted SADs of the dword group as 16-bit
             // sums (a quadrant's is <= 8 * 8 * 255), a v_qsad_pk_u16_u8 per source dword and row
             uint64_t acc[4] = {0, 0, 0, 0};
+#pragma unroll
+            for (int h = 0; h < 2; ++h)  // the top quadrants' rows, then the bottom ones'
 #pragma unroll 2
-            for (int r = 0; r < 16; ++r) {
-                const int a = (dyr + r) * kWs4 + g, hq = r < 8 ? 0 : 2;
-                const uint32_t w0 = win32[a], w1 = win32[a + 1], w2 = win32[a + 2], w3 = win32[a + 3], w4 = win32[a + 4];
-                const uint32_t s0 = srcw[r * 4 + 0], s1 = srcw[r * 4 + 1], s2 = srcw[r * 4 + 2], s3 = srcw[r * 4 + 3];
-                uint64_t lft = hq ? acc[2] : acc[0], rgt = hq ? acc[3] : acc[1];
-                lft = qsad4(w1, w0, s0, lft);
-                lft = qsad4(w2, w1, s1, lft);
-                rgt = qsad4(w3, w2, s2, rgt);
-                rgt = qsad4(w4, w3, s3, rgt);
-                if (hq) {
-                    acc[2] = lft;
-                    acc[3] = rgt;
-                } else {
-                    acc[0] = lft;
-                    acc[1] = rgt;
-                }
-            }
+                for (int r = 8 * h; r < 8 * h + 8; ++r)
+                    me_row(win32, srcw, (dyr + r) * kWs4 + g, r, acc[2 * h], acc[2 * h + 1]);
 #pragma unroll
             for (int si = 0; si < 4; ++si) {
                 if (si >= nsh) break;
@@ -450,97 +560,38 @@ __device__ __forceinline__ MbInfo me_full_body(const Geometry& g, const MeState&
                 visit_quads(qd, dxr, dyr);
             }
         }
+    } else {
+        auto visit = [&](uint32_t sad, int dxr, int dyr) { best = kmin(best, mkey(sad, dxr, dyr)); };
+        if (coarse)
+            me_score16<true>(win32, srcw, (R + 1) * gw, gw, side, tid, visit);
+        else
+            me_score16<false>(win32, srcw, ngroups, gw, side, tid, visit);
     }
-    for (int q = tid; q < ntask; q += kMeThreads) {
-        const int dyr = 2 * (q / gw), g = q % gw;
-        uint64_t acc = 0;  // four shifted 16x16 SADs, 16 bits each (<= 65,280); shifts 0 and 2 are used
-#pragma unroll 4
-        for (int r = 0; r < 16; ++r) {
-            const int a = (dyr + r) * kWs4 + g;
-            const uint32_t w0 = win32[a], w1 = win32[a + 1], w2 = win32[a + 2], w3 = win32[a + 3], w4 = win32[a + 4];
-            const uint32_t s0 = srcw[r * 4 + 0], s1 = srcw[r * 4 + 1], s2 = srcw[r * 4 + 2], s3 = srcw[r * 4 + 3];
-            acc = qsad4(w1, w0, s0, acc);
-            acc = qsad4(w2, w1, s1, acc);
-            acc = qsad4(w3, w2, s2, acc);
-            acc = qsad4(w4, w3, s3, acc);
-        }
-        const uint32_t s0a = (uint32_t)acc & 0xffffu, s2a = (uint32_t)(acc >> 32) & 0xffffu;
-#pragma unroll
-        for (int h2 = 0; h2 < 2; ++h2) {
-            const int dxr = 4 * g + 2 * h2;
-            if (dxr >= side) break;
-            const int dx = dxr - R, dy = dyr - R, c = dyr * side + dxr;
-            const uint32_t cost = me_cost(h2 ? s2a : s0a, lambda, 4 * dx, 4 * dy);
-            const uint32_t dist = (uint32_t)(abs(dx) + abs(dy));
-            const unsigned long long key = ((unsigned long long)cost << 32) | (dist << 16) | (uint32_t)c;
-            best = key < best ? key : best;
-        }
-    }
-    for (int q = tid; q < ((coarse || parts) ? 0 : ngroups); q += kMeThreads) {
-        const int dyr = q / gw, g = q - dyr * gw;
-        uint64_t acc = 0;  // four shifted 16x16 SADs, 16 bits each
-#pragma unroll 2
-        for (int r = 0; r < 16; ++r) {
-            const int a = (dyr + r) * kWs4 + g;
-            const uint32_t w0 = win32[a], w1 = win32[a + 1], w2 = win32[a + 2], w3 = win32[a + 3], w4 = win32[a + 4];
-            const uint32_t s0 = srcw[r * 4 + 0], s1 = srcw[r * 4 + 1], s2 = srcw[r * 4 + 2], s3 = srcw[r * 4 + 3];
-            acc = qsad4(w1, w0, s0, acc);
-            acc = qsad4(w2, w1, s1, acc);
-            acc = qsad4(w3, w2, s2, acc);
-            acc = qsad4(w4, w3, s3, acc);
-        }
-        const uint32_t sad[4] = {(uint32_t)acc & 0xffffu, (uint32_t)(acc >> 16) & 0xffffu,
-                                 (uint32_t)(acc >> 32) & 0xffffu, (uint32_t)(acc >> 48) & 0xffffu};
-#pragma unroll
-        for (int sh = 0; sh < 4; ++sh) {
-            const int dxr = 4 * g + sh;
-            if (dxr >= side) break;
-            const int dx = dxr - R, dy = dyr - R, c = dyr * side + dxr;
-            const uint32_t cost = me_cost(sad[sh], lambda, 4 * dx, 4 * dy);
-            const uint32_t dist = (uint32_t)(abs(dx) + abs(dy));
-            const unsigned long long key = ((unsigned long long)cost << 32) | (dist << 16) | (uint32_t)c;
-            best = key < best ? key : best;
-        }
-    }
-    for (int o = 32; o > 0; o >>= 1) {
-        unsigned long long other = __shfl_xor(best, o, 64);
-        best = other < best ? other : best;
-    }
+    best = wave_min_u64(best);
     if (lane == 0) red[tid >> 6] = best;
     __shared__ unsigned long long pred4[4][kMeWaves];  // partitions: [shape][wave]
     if (parts) {
 #pragma unroll
         for (int sh = 0; sh < 4; ++sh) {
-            unsigned long long v = pb[sh];
-            for (int o = 32; o > 0; o >>= 1) {
-                const unsigned long long other = __shfl_xor(v, o, 64);
-                v = other < v ? other : v;
-            }
+            const unsigned long long v = wave_min_u64(pb[sh]);
             if (lane == 0) pred4[sh][tid >> 6] = v;
         }
     }
     __syncthreads();
-    unsigned long long b = red[0];
-    for (int i = 1; i < kMeWaves; ++i) b = red[i] < b ? red[i] : b;
+    unsigned long long b = block_min(red);
     unsigned long long pbest[4] = {~0ull, ~0ull, ~0ull, ~0ull};
     if (parts)
-        for (int sh = 0; sh < 4; ++sh)
-            for (int i = 0; i < kMeWaves; ++i) pbest[sh] = pred4[sh][i] < pbest[sh] ? pred4[sh][i] : pbest[sh];
+        for (int sh = 0; sh < 4; ++sh) pbest[sh] = block_min(pred4[sh]);
+    const uint8_t* wb = reinterpret_cast<const uint8_t*>(win32);
+    const uint8_t* sb = reinterpret_cast<const uint8_t*>(srcw);
     if (parts && coarse) {
         // the 8 integer neighbours of each partition's grid best: 32 (shape, neighbour) pairs of
         // 128-sample rectangles, 8 lanes (16 samples) each
         __shared__ unsigned long long pnkey[4][8];
-        const int ev = (tid & 255) >> 3, sub = tid & 7, sh = ev >> 3, k = ev & 7;
-        const int cb0 = (int)(pbest[sh] & 0xffff), bxr = cb0 % side, byr = cb0 / side;
-        int ddx, ddy;
-        subpel_offset(k, &ddx, &ddy);
-        const int nxr = bxr + ddx, nyr = byr + ddy;
-        const bool inside = t256 && nxr >= 0 && nxr < side && nyr >= 0 && nyr < side;  // uniform per 8-lane group
-        int d = 0;
-        if (inside) {
+        const int ev = tid >> 3, sub = tid & 7, sh = ev >> 3, k = ev & 7;
+        const unsigned long long nk = me_neighbour<8>(pbest[sh], k, side, [&](int nxr, int nyr) {
             // T / B: one 16-sample row each (row sub of the half); L / R: two 8-sample rows
-            const uint8_t* wb = reinterpret_cast<const uint8_t*>(win32);
-            const uint8_t* sb = reinterpret_cast<const uint8_t*>(srcw);
+            int d = 0;
             for (int part_row = 0; part_row < 2; ++part_row) {
                 const int rr = sh < 2 ? (sh == 0 ? sub : 8 + sub) : 2 * sub + part_row;
                 const int c0 = sh < 2 ? 8 * part_row : (sh == 2 ? 0 : 8);
@@ -548,37 +599,27 @@ __device__ __forceinline__ MbInfo me_full_body(const Geometry& g, const MeState&
                 for (int j = 0; j < 8; ++j)
                     d += abs((int)sb[rr * 16 + c0 + j] - (int)wb[(nyr + rr) * kWinStride + nxr + c0 + j]);
             }
-        }
-        for (int o = 4; o > 0; o >>= 1) d += __shfl_xor(d, o, 64);
-        if (t256 && sub == 0) pnkey[sh][k] = inside ? mkey((uint32_t)d, nxr, nyr) : ~0ull;
+            return d;
+        }, mkey);
+        if (sub == 0) pnkey[sh][k] = nk;
         __syncthreads();
         for (int s2 = 0; s2 < 4; ++s2)
-            for (int i = 0; i < 8; ++i) pbest[s2] = pnkey[s2][i] < pbest[s2] ? pnkey[s2][i] : pbest[s2];
+            for (int i = 0; i < 8; ++i) pbest[s2] = kmin(pbest[s2], pnkey[s2][i]);
     }
-    if (coarse) {  // the 8 integer neighbours of the grid best: one per 32-lane group
+    if (coarse) {  // the 8 integer neighbours of the grid best: one per 32-lane group, 8 samples per lane
         __shared__ unsigned long long nkey[8];
-        const int cb0 = (int)(b & 0xffff), bxr = cb0 % side, byr = cb0 / side;
-        const int k = (tid & 255) >> 5, sub = tid & 31, py = sub >> 1, px0 = (sub & 1) * 8;
-        int ddx, ddy;
-        subpel_offset(k, &ddx, &ddy);
-        const int nxr = bxr + ddx, nyr = byr + ddy;
-        const bool inside = t256 && nxr >= 0 && nxr < side && nyr >= 0 && nyr < side;  // uniform per group
-        int d = 0;
-        if (inside) {
-            const uint8_t* wrow = reinterpret_cast<const uint8_t*>(win32) + (nyr + py) * kWinStride + nxr + px0;
+        const int k = tid >> 5, sub = tid & 31, py = sub >> 1, px0 = (sub & 1) * 8;
+        const unsigned long long nk = me_neighbour<32>(b, k, side, [&](int nxr, int nyr) {
+            const uint8_t* wrow = wb + (nyr + py) * kWinStride + nxr + px0;
             const uint32_t s0 = srcw[py * 4 + (px0 >> 2)], s1 = srcw[py * 4 + (px0 >> 2) + 1];
+            int d = 0;
 #pragma unroll
-            for (int j = 0; j < 8; ++j) d += abs((int)(((j < 4 ? s0 : s1) >> (8 * (j & 3))) & 0xff) - (int)wrow[j]);
-        }
-        for (int o = 16; o > 0; o >>= 1) d += __shfl_xor(d, o, 64);
-        if (t256 && sub == 0) {
-            const int dx = nxr - R, dy = nyr - R;
-            const uint32_t cost = me_cost((uint32_t)d, lambda, 4 * dx, 4 * dy);
-            const uint32_t dist = (uint32_t)(abs(dx) + abs(dy));
-            nkey[k] = inside ? (((unsigned long long)cost << 32) | (dist << 16) | (uint32_t)(nyr * side + nxr)) : ~0ull;
-        }
+            for (int j = 0; j < 8; ++j) d += abs(byte_of(j < 4 ? s0 : s1, j & 3) - (int)wrow[j]);
+            return d;
+        }, mkey);
+        if (sub == 0) nkey[k] = nk;
         __syncthreads();
-        for (int i = 0; i < 8; ++i) b = nkey[i] < b ? nkey[i] : b;
+        for (int i = 0; i < 8; ++i) b = kmin(b, nkey[i]);
     }
     const int cbest = (int)(b & 0xffff);
     int mvx = 4 * ((cbest % side) - R), mvy = 4 * ((cbest / side) - R);
@@ -603,70 +644,18 @@ __device__ __forceinline__ MbInfo me_full_body(const Geometry& g, const MeState&
             if (st.subpel) {
                 // half then quarter pel per partition over its own rectangle: an 18x18 footprint
                 // per partition, 16 lanes (8 samples each) per candidate, both partitions at once
-                uint8_t(*psp)[4][18][kSpW] = sp2;
                 __shared__ uint32_t pcand[2][8];
                 build_footprints(reinterpret_cast<const uint8_t*>(win_lds), fp_org(pvx[0], pvy[0]),
                                  fp_org(pvx[1], pvy[1]), 2, sp2, fp_b1, tid);
                 __syncthreads();
-                const int pi = (tid & 255) >> 7, k = (tid >> 4) & 7, sub = tid & 15;
+                const int pi = tid >> 7, k = (tid >> 4) & 7, sub = tid & 15;
                 // the 8 samples of this lane inside the partition rectangle
                 const int rx = part == kPart8x16 ? 8 * pi : 0, ry = part == kPart16x8 ? 8 * pi : 0;
                 const int prow = part == kPart16x8 ? (sub >> 1) : sub, pcol = part == kPart16x8 ? (sub & 1) * 8 : 0;
-                const int yy = ry + prow, xx = rx + pcol;
-                const uint32_t s0w = srcw[yy * 4 + (xx >> 2)], s1w = srcw[yy * 4 + (xx >> 2) + 1];
-                const int ivx = pvx[pi], ivy = pvy[pi];  // the integer match the footprint is staged around
-                const int base_x4 = xx * 4 + 4 - ivx, base_y4 = yy * 4 + 4 - ivy;
-                for (int step = 2; step >= 1; step >>= 1) {
-                    int ddx, ddy;
-                    subpel_offset(k, &ddx, &ddy);
-                    const int cx = pvx[pi] + ddx * step, cy = pvy[pi] + ddy * step;
-                    int d = 0;
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) {
-                        const int sv = (int)(((j < 4 ? s0w : s1w) >> (8 * (j & 3))) & 0xff);
-                        d += abs(sv - qpel_lds(psp[pi], base_x4 + 4 * j + cx, base_y4 + cy));
-                    }
-                    for (int o = 8; o > 0; o >>= 1) d += __shfl_xor(d, o, 64);
-                    __syncthreads();  // the previous step's readers are done with pcand
-                    if (t256 && sub == 0) pcand[pi][k] = me_cost((uint32_t)d, lambda, cx, cy);
-                    __syncthreads();
-                    for (int q = 0; q < 2; ++q) {
-                        int bdx = 0, bdy = 0;
-                        uint32_t bcost = pcost[q];
-                        for (int kk = 0; kk < 8; ++kk) {
-                            const uint32_t cc = pcand[q][kk];
-                            if (cc < bcost) {
-                                int ex, ey;
-                                subpel_offset(kk, &ex, &ey);
-                                bcost = cc;
-                                bdx = ex * step;
-                                bdy = ey * step;
-                            }
-                        }
-                        pvx[q] += bdx;
-                        pvy[q] += bdy;
-                        pcost[q] = bcost;
-                    }
-                }
+                me_refine<2>(sp2, pcand, srcw, pi, k, sub, rx + pcol, ry + prow, lambda, pvx, pvy, pcost);
             }
-            if (tid == 0) {
-                MbInfo& m = mbs[mbi];
-                m.mvx = (int16_t)(4 * cx + mvx);  // the integer 16x16 vector (unused by the partitioned MB)
-                m.mvy = (int16_t)(4 * cy + mvy);
-                m.part = (uint8_t)part;
-                m.pmv[0] = (int16_t)(4 * cx + pvx[0]);
-                m.pmv[1] = (int16_t)(4 * cy + pvy[0]);
-                m.pmv[2] = (int16_t)(4 * cx + pvx[1]);
-                m.pmv[3] = (int16_t)(4 * cy + pvy[1]);
-            }
-            out.mvx = (int16_t)(4 * cx + mvx);
-            out.mvy = (int16_t)(4 * cy + mvy);
-            out.part = (uint8_t)part;
-            out.pmv[0] = (int16_t)(4 * cx + pvx[0]);
-            out.pmv[1] = (int16_t)(4 * cy + pvy[0]);
-            out.pmv[2] = (int16_t)(4 * cx + pvx[1]);
-            out.pmv[3] = (int16_t)(4 * cy + pvy[1]);
-            return out;  // uniform
+            // mvx, mvy: the integer 16x16 vector (unused by the partitioned MB)
+            return store_motion(mbs, mbi, tid, cx, cy, mvx, mvy, part, pvx, pvy);  // uniform
         }
     }
 
@@ -676,55 +665,13 @@ __device__ __forceinline__ MbInfo me_full_body(const Geometry& g, const MeState&
         // interpolated once from the staged window; the 8 neighbours of a step are
         // scored at once, one per 32-lane half-wave group (8 pixels per lane, source from
         // srcw), a 5-step xor shuffle reduces each group, one barrier publishes the costs.
-        uint8_t(*sp)[18][kSpW] = sp2[0];
         build_footprints(reinterpret_cast<const uint8_t*>(win_lds), fp_org(mvx, mvy), 0, 1, sp2, fp_b1, tid);
         __syncthreads();
         uint32_t cur_cost = (uint32_t)(b >> 32);
-        const int k = (tid & 255) >> 5, sub = tid & 31;
-        const int py = sub >> 1, px0 = (sub & 1) * 8;
-        const uint32_t s0 = srcw[py * 4 + (px0 >> 2)], s1 = srcw[py * 4 + (px0 >> 2) + 1];
-        const int base_x4 = px0 * 4 + 4 - mvx, base_y4 = py * 4 + 4 - mvy;  // local qpel coords = base + candidate mv
-        for (int step = 2; step >= 1; step >>= 1) {
-            int ddx, ddy;
-            subpel_offset(k, &ddx, &ddy);
-            const int cx = mvx + ddx * step, cy = mvy + ddy * step;
-            int d = 0;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const int sv = (int)(((j < 4 ? s0 : s1) >> (8 * (j & 3))) & 0xff);
-                d += abs(sv - qpel_lds(sp, base_x4 + 4 * j + cx, base_y4 + cy));
-            }
-            for (int o = 16; o > 0; o >>= 1) d += __shfl_xor(d, o, 64);
-            __syncthreads();  // previous step's readers are done with cand_cost
-            if (t256 && sub == 0) cand_cost[k] = me_cost((uint32_t)d, lambda, cx, cy);
-            __syncthreads();
-            int bdx = 0, bdy = 0;
-            uint32_t bcost = cur_cost;
-            for (int kk = 0; kk < 8; ++kk) {
-                const uint32_t cc = cand_cost[kk];
-                if (cc < bcost) {
-                    int ex, ey;
-                    subpel_offset(kk, &ex, &ey);
-                    bcost = cc;
-                    bdx = ex * step;
-                    bdy = ey * step;
-                }
-            }
-            mvx += bdx;
-            mvy += bdy;
-            cur_cost = bcost;
-        }
+        const int k = tid >> 5, sub = tid & 31;
+        me_refine<1>(sp2, &cand_cost, srcw, 0, k, sub, (sub & 1) * 8, sub >> 1, lambda, &mvx, &mvy, &cur_cost);
     }
-    if (tid == 0) {
-        MbInfo& m = mbs[mbi];
-        m.mvx = (int16_t)(4 * cx + mvx);
-        m.mvy = (int16_t)(4 * cy + mvy);
-        m.part = kPart16x16;
-        m.pmv[0] = m.pmv[1] = m.pmv[2] = m.pmv[3] = 0;
-    }
-    out.mvx = (int16_t)(4 * cx + mvx);
-    out.mvy = (int16_t)(4 * cy + mvy);
-    return out;
+    return store_motion(mbs, mbi, tid, cx, cy, mvx, mvy);
 }
 
 // The search is the first kernel of an H.264 P picture: it publishes the frame state for the later
@@ -795,13 +742,11 @@ __global__ __launch_bounds__(kProbeThreads) void k_scroll_probe(Geometry g, Stat
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int npx = scroll_probes_x(g.mb_w);
     const int x0 = (int)(blockIdx.x % npx) * kScrollLattice * 16, y0 = (int)(blockIdx.x / npx) * kScrollLattice * 16;
-    if (tid < 64) {  // the static exit of the search: one dword of source and reference per lane
-        const int r = tid >> 2, c4 = (tid & 3) * 4;
-        const uint32_t sw = *reinterpret_cast<const uint32_t*>(src_y + (y0 + r) * g.pitch + x0 + c4);
-        const uint32_t rw = *reinterpret_cast<const uint32_t*>(ref + (y0 + r) * g.pitch + x0 + c4);
+    if (tid < 64) {  // the static exit of the search
+        uint32_t sw;
+        const uint32_t d = zero_sad_wave(src_y, ref, g.pitch, x0, y0, tid, &sw);
         srcw[tid] = sw;
-        const int d = wave_sum((int)__builtin_amdgcn_sad_u8(sw, rw, 0u));
-        if (tid == 0) s_flag[0] = (uint32_t)d;
+        if (tid == 0) s_flag[0] = d;
     }
     __syncthreads();
     if (s_flag[0] > static_sad(qp)) {  // uniform across the workgroup

@@ -61,6 +61,14 @@ __device__ __forceinline__ uint32_t wave_or(uint32_t v) {
     xrow32(a | b, a, b);
     return a | b;
 }
+// Wave minimum of a 64-bit key, every lane gets it: an xor-shuffle ladder (two dwords per step).
+__device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v) {
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned long long other = __shfl_xor(v, o, 64);
+        v = other < v ? other : v;
+    }
+    return v;
+}
 
 // LDS hand-off between the lanes of ONE wave (its own LDS writes visible to its own later reads;
 // LDS operations of a wave complete in order): no workgroup barrier, so the waves of a workgroup

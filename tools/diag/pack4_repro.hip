@@ -1,4 +1,4 @@
-// Stand-alone reduction of the byte-packing miscompile recorded at h264_kernels.hip:140-148
+// Stand-alone reduction of the byte-packing miscompile recorded at pack4() (csrc/codec/h264_kernels.hip)
 // (VERDICT r2 #8): four 6-tap filter outputs, clamped to 8 bits, OR-ed into one dword as
 // `clip255(v) << 8 * j`.  On the MI355X the hpel kernel built this way produced 0xff in bytes
 // 2-3 whenever sample 1 clamped from below to 0.  Three packings of the same values are
