@@ -287,6 +287,19 @@ PYBIND11_MODULE(_native, m) {
                      for (int k = 0; k < 4; ++k) d[4 * i + k] = v[i].pmv[k];
                  return a.reshape({e.common().mb_h(), e.common().mb_w(), 4});
              })
+        .def("mb_pmv8",
+             [](h264::CpuH264Encoder& e) {  // (mb_h, mb_w, 8): the vectors of quadrants TL, TR, BL, BR (part == 3; else 0)
+                 const auto& v = e.mb_info();
+                 py::array_t<int32_t> a({(py::ssize_t)v.size(), (py::ssize_t)8});
+                 int32_t* d = a.mutable_data();
+                 for (size_t i = 0; i < v.size(); ++i)
+                     for (int q = 0; q < 4; ++q) {
+                         const h264::Mv mv = v[i].part == h264::kPart8x8 ? h264::quad_mv(v[i], q) : h264::Mv{0, 0};
+                         d[8 * i + 2 * q] = mv.x;
+                         d[8 * i + 2 * q + 1] = mv.y;
+                     }
+                 return a.reshape({e.common().mb_h(), e.common().mb_w(), 8});
+             })
         .def("mb_scroll_path",
              [](h264::CpuH264Encoder& e) {  // (mb_h, mb_w) of the last P picture: MeScrollPath per macroblock
                  const auto& v = e.mb_scroll_path();

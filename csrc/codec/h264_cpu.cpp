@@ -171,10 +171,14 @@ void me_search_cpu(const uint8_t* sy, int pitch, const uint8_t* ref_y, int cw_, 
 //  * shape: 16x16 unless a partitioning's two costs + 2 lambda (mb_type ue(1) / ue(2) vs ue(0))
 //    are lower (16x8 before 8x16 on ties);
 //  * quarter-pel refinement (half, then quarter) of the chosen shape's vector(s), each over its
-//    own rectangle.
+//    own rectangle;
+//  * quads (EncoderConfig::partitions 2): each 8x8 quadrant keeps a best of its own as well, and
+//    P_8x8 (one vector per quadrant) is taken when its four costs + 8 lambda (mb_type ue(3) and four
+//    sub_mb_type ue(0): 9 bits against 1) are strictly lower than every other shape's cost.  The
+//    static exit and the scroll exit stay 16x16.
 void me_search_parts_cpu(const uint8_t* sy, int pitch, const uint8_t* ref_y, int cw_, int ch_, int x0, int y0,
                          int frame_qp, int search_range, int subpel, int coarse, MbInfo& m, int gx, int gy,
-                         uint8_t* path) {
+                         uint8_t* path, bool quads8) {
     const int lambda = lambda_sad(frame_qp);
     const int R = me_range(search_range);
     const int side = 2 * R + 1;
@@ -199,7 +203,8 @@ void me_search_parts_cpu(const uint8_t* sy, int pitch, const uint8_t* ref_y, int
         }
         if (use == kScrollCentre) cx = gx, cy = gy;
     }
-    // shapes: 0 = 16x16, 1 = top, 2 = bottom, 3 = left, 4 = right (quadrants TL, TR, BL, BR)
+    // shapes: 0 = 16x16, 1 = top, 2 = bottom, 3 = left, 4 = right, 5..8 = quadrants TL, TR, BL, BR
+    const int ns = quads8 ? 9 : 5;
     auto quads = [&](int c, uint32_t q[4]) {
         const int dy = c / side - R, dx = c % side - R;
         q[0] = q[1] = q[2] = q[3] = 0;
@@ -214,7 +219,8 @@ void me_search_parts_cpu(const uint8_t* sy, int pitch, const uint8_t* ref_y, int
             case 1: return q[0] + q[1];
             case 2: return q[2] + q[3];
             case 3: return q[0] + q[2];
-            default: return q[1] + q[3];
+            case 4: return q[1] + q[3];
+            default: return q[s - 5];
         }
     };
     auto key = [&](uint32_t sad, int c) {
@@ -223,18 +229,18 @@ void me_search_parts_cpu(const uint8_t* sy, int pitch, const uint8_t* ref_y, int
         const uint32_t dist = (uint32_t)(std::abs(dx) + std::abs(dy));
         return ((unsigned long long)cost << 32) | (dist << 16) | (uint32_t)c;
     };
-    unsigned long long best[5] = {~0ull, ~0ull, ~0ull, ~0ull, ~0ull};
+    unsigned long long best[9] = {~0ull, ~0ull, ~0ull, ~0ull, ~0ull, ~0ull, ~0ull, ~0ull, ~0ull};
     auto visit = [&](int c, unsigned long long* b) {
         uint32_t q[4];
         quads(c, q);
-        for (int s = 0; s < 5; ++s) b[s] = std::min(b[s], key(shape_sad(q, s), c));
+        for (int s = 0; s < ns; ++s) b[s] = std::min(b[s], key(shape_sad(q, s), c));
     };
     if (coarse) {
         for (int dyr = 0; dyr < side; dyr += 2)
             for (int dxr = 0; dxr < side; dxr += 2) visit(dyr * side + dxr, best);
-        unsigned long long nb[5];
-        for (int s = 0; s < 5; ++s) nb[s] = best[s];
-        for (int s = 0; s < 5; ++s) {
+        unsigned long long nb[9];
+        for (int s = 0; s < ns; ++s) nb[s] = best[s];
+        for (int s = 0; s < ns; ++s) {
             const int cb0 = (int)(best[s] & 0xffff), bxr = cb0 % side, byr = cb0 / side;
             for (int k = 0; k < 8; ++k) {
                 int ddx, ddy;
@@ -246,7 +252,7 @@ void me_search_parts_cpu(const uint8_t* sy, int pitch, const uint8_t* ref_y, int
                 nb[s] = std::min(nb[s], key(shape_sad(q, s), nyr * side + nxr));
             }
         }
-        for (int s = 0; s < 5; ++s) best[s] = nb[s];
+        for (int s = 0; s < ns; ++s) best[s] = nb[s];
     } else {
         for (int c = 0; c < side * side; ++c) visit(c, best);
     }
@@ -254,9 +260,14 @@ void me_search_parts_cpu(const uint8_t* sy, int pitch, const uint8_t* ref_y, int
     const uint32_t c16 = cost_of(best[0]);
     const uint32_t ch = cost_of(best[1]) + cost_of(best[2]) + 2u * (uint32_t)lambda;
     const uint32_t cv = cost_of(best[3]) + cost_of(best[4]) + 2u * (uint32_t)lambda;
-    const int part = (c16 <= ch && c16 <= cv) ? kPart16x16 : (ch <= cv ? kPart16x8 : kPart8x16);
+    int part = (c16 <= ch && c16 <= cv) ? kPart16x16 : (ch <= cv ? kPart16x8 : kPart8x16);
+    if (quads8) {
+        const uint32_t c8 = cost_of(best[5]) + cost_of(best[6]) + cost_of(best[7]) + cost_of(best[8]) + 8u * (uint32_t)lambda;
+        if (c8 < c16 && c8 < ch && c8 < cv) part = kPart8x8;
+    }
     // rectangle of each shape (x, y, w, h) and the refinement
-    constexpr int kRect[5][4] = {{0, 0, 16, 16}, {0, 0, 16, 8}, {0, 8, 16, 8}, {0, 0, 8, 16}, {8, 0, 8, 16}};
+    constexpr int kRect[9][4] = {{0, 0, 16, 16}, {0, 0, 16, 8}, {0, 8, 16, 8}, {0, 0, 8, 16}, {8, 0, 8, 16},
+                                 {0, 0, 8, 8},   {8, 0, 8, 8},  {0, 8, 8, 8},  {8, 8, 8, 8}};
     auto refine = [&](int s, int* vx, int* vy) {
         const int cb = (int)(best[s] & 0xffff);
         *vx = 4 * ((cb % side) - R);
@@ -296,6 +307,14 @@ void me_search_parts_cpu(const uint8_t* sy, int pitch, const uint8_t* ref_y, int
         refine(0, &vx, &vy);
         m.mvx = (int16_t)(4 * cx + vx);
         m.mvy = (int16_t)(4 * cy + vy);
+        return;
+    }
+    if (part == kPart8x8) {
+        m.part = (uint8_t)part;
+        for (int q = 0; q < 4; ++q) {
+            refine(5 + q, &vx, &vy);
+            set_quad_mv(m, q, 4 * cx + vx, 4 * cy + vy);
+        }
         return;
     }
     const int cb = (int)(best[0] & 0xffff);  // the 16x16 vector stays integer here
@@ -512,7 +531,7 @@ void CpuH264Encoder::encode_inter(const uint8_t* sy, const uint8_t* suv, int pit
             std::memset(&m, 0, sizeof m);
             if (cfg_.partitions) {
                 me_search_parts_cpu(sy, pitch, me_ref, cw_, ch_, x0, y0, frame_qp, cfg_.search_range, cfg_.subpel,
-                                    cfg_.me_coarse, m, gx, gy, &mb_path_[mbi]);
+                                    cfg_.me_coarse, m, gx, gy, &mb_path_[mbi], cfg_.partitions >= 2);
             } else {
                 int vx = 0, vy = 0;
                 me_search_cpu(sy, pitch, me_ref, cw_, ch_, x0, y0, frame_qp, cfg_.search_range, cfg_.subpel, &vx, &vy,
@@ -696,7 +715,7 @@ void CpuH264Encoder::entropy(std::vector<uint8_t>& payload, std::vector<uint32_t
         int qp_pred = frame_qp_();  // mb_qp_delta predictor: QP of the last MB that carried one
         for (int mbi = first; mbi < last; ++mbi) {
             const Avail av = mb_avail(g, mbi % g.mb_w, mbi / g.mb_w, slice_rows);
-            int mvd[4];
+            int mvd[8];
             const MbNbrs nb = mb_nbrs(mb_.data(), mbi, g.mb_w);
             const bool skip = decide_skip(nb, av, mvd);
             mb_[mbi].skip = skip;

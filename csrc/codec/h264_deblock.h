@@ -31,9 +31,21 @@ constexpr uint8_t kDbTc0[52][3] = {
 MXHD int db_abs(int v) { return v < 0 ? -v : v; }
 MXHD int db_clip3(int lo, int hi, int v) { return v < lo ? lo : (v > hi ? hi : v); }
 
-// Motion vector of raster 4x4 block `blk` (by * 4 + bx) of an inter macroblock.
+// Motion vector of raster 4x4 block `blk` (by * 4 + bx) of an inter macroblock: blk_mv (h264_mb.h)
+// for the strengths.  kQuad false: the picture was searched without quadrants and holds no P_8x8
+// macroblock (k_db_prep<false>; k_db_prep<true> and the CPU encoder pass true) -- the function is then what
+// it was.  With kQuad the vectors of a P_8x8 macroblock's quadrants TL, TR, BL, BR (h264_gpu.h MbInfo)
+// are read first and chosen by value: a choice between the fields' addresses keeps MbInfo in scratch.
+template <bool kQuad = true>
 MXHD void db_blk_mv(const MbInfo& m, int blk, int* mvx, int* mvy) {
     const int bx = blk & 3, by = blk >> 2;
+    if (kQuad && m.part == kPart8x8) {
+        const int x0 = m.mvx, y0 = m.mvy, x1 = m.pmv[0], y1 = m.pmv[1], x2 = m.pmv[2], y2 = m.pmv[3], x3 = m.pmv3[0], y3 = m.pmv3[1];
+        const bool right = bx >= 2, low = by >= 2;
+        *mvx = low ? (right ? x3 : x2) : (right ? x1 : x0);
+        *mvy = low ? (right ? y3 : y2) : (right ? y1 : y0);
+        return;
+    }
     const bool second = (m.part == kPart16x8 && by >= 2) || (m.part == kPart8x16 && bx >= 2);
     if (m.part == kPart16x16) {
         *mvx = m.mvx;
@@ -46,26 +58,30 @@ MXHD void db_blk_mv(const MbInfo& m, int blk, int* mvx, int* mvy) {
 
 // Boundary strength (8.7.2.1) of the edge between raster 4x4 luma block bp of macroblock p and
 // block bq of macroblock q (frame macroblocks, every inter block refers to picture 0).
+template <bool kQuad = true>
 MXHD int db_bs(const MbInfo& p, int bp, const MbInfo& q, int bq, bool mb_edge) {
     if (is_intra(p) || is_intra(q)) return mb_edge ? 4 : 3;
     if (p.nz_luma[bp] || q.nz_luma[bq]) return 2;
     int px, py, qx, qy;
-    db_blk_mv(p, bp, &px, &py);
-    db_blk_mv(q, bq, &qx, &qy);
+    db_blk_mv<kQuad>(p, bp, &px, &py);
+    db_blk_mv<kQuad>(q, bq, &qx, &qy);
     return (db_abs(px - qx) >= 4 || db_abs(py - qy) >= 4) ? 1 : 0;
 }
 
 // The four bS values (one per 4-sample segment) of luma edge e (0..3) of macroblock q, vertical
 // (left / internal column edges) or horizontal (top / internal row edges), packed 3 bits each;
 // nb = the left (vertical) or top (horizontal) macroblock for e == 0, nullptr = picture edge.
+template <bool kQuad = true>
 MXHD uint32_t db_edge_bs4(const MbInfo& q, const MbInfo* nb, int e, bool vertical) {
     uint32_t out = 0;
     for (int s = 0; s < 4; ++s) {
         int bs;
         if (vertical) {
-            bs = e == 0 ? (nb ? db_bs(*nb, s * 4 + 3, q, s * 4, true) : 0) : db_bs(q, s * 4 + e - 1, q, s * 4 + e, false);
+            bs = e == 0 ? (nb ? db_bs<kQuad>(*nb, s * 4 + 3, q, s * 4, true) : 0)
+                        : db_bs<kQuad>(q, s * 4 + e - 1, q, s * 4 + e, false);
         } else {
-            bs = e == 0 ? (nb ? db_bs(*nb, 12 + s, q, s, true) : 0) : db_bs(q, (e - 1) * 4 + s, q, e * 4 + s, false);
+            bs = e == 0 ? (nb ? db_bs<kQuad>(*nb, 12 + s, q, s, true) : 0)
+                        : db_bs<kQuad>(q, (e - 1) * 4 + s, q, e * 4 + s, false);
         }
         out |= (uint32_t)bs << (3 * s);
     }
@@ -155,20 +171,30 @@ MXHD void db_chroma_line(int p1, int& p0, int& q0, int q1, int bs, const DbParam
 struct DbAutoCounts {
     uint32_t coherent = 0, changed = 0, moving = 0;
 };
+// kQuad false: no macroblock of the picture is P_8x8 (k_scan_rows<false>): the rule is what it was.
+template <bool kQuad = true>
 MXHD void db_auto_count(const MbInfo* mbs, int mb_w, int i, DbAutoCounts& c) {
     const MbInfo& m = mbs[i];
     if (is_intra(m)) {
         ++c.changed;
         return;
     }
-    const bool moving = m.mvx != 0 || m.mvy != 0;
+    // A P_8x8 macroblock (part 3) has no 16x16 vector: it is moving when any quadrant's vector is
+    // non-zero and never coherent -- four vectors are a window's corner or a seam, not a pan -- and
+    // no neighbour is coherent with it.
+    const bool quad = kQuad && m.part == kPart8x8;
+    const bool moving = m.mvx != 0 || m.mvy != 0 ||
+                        (quad && (m.pmv[0] | m.pmv[1] | m.pmv[2] | m.pmv[3] | m.pmv3[0] | m.pmv3[1]) != 0);
     if (!moving) {
         if (m.cbp) ++c.changed;
         return;
     }
     ++c.moving;
+    if (quad) return;
     const int x = i % mb_w;
-    auto same = [&](const MbInfo& n) { return !is_intra(n) && n.mvx == m.mvx && n.mvy == m.mvy; };
+    auto same = [&](const MbInfo& n) {
+        return !is_intra(n) && !(kQuad && n.part == kPart8x8) && n.mvx == m.mvx && n.mvy == m.mvy;
+    };
     if ((x > 0 && same(mbs[i - 1])) || (i >= mb_w && same(mbs[i - mb_w]))) ++c.coherent;
 }
 // The coherent count from motion vectors alone (HEVC: the 16x16 motion-search vectors of its

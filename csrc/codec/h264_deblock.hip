@@ -68,6 +68,9 @@ __device__ __forceinline__ uint32_t rec_edge(const uint4& r, int dir, int e) {
     return (w >> (12 * (e & 1))) & 0xfffu;
 }
 
+// kQuad: the picture may hold P_8x8 macroblocks (EncoderConfig::partitions 2).  A template kernel: behind a
+// shared device function k_db_prep<false> no longer compiled to the instructions k_db_prep had.
+template <bool kQuad>
 __global__ __launch_bounds__(256) void k_db_prep(Geometry g, const FrameState* __restrict__ fs,
                                                  const MbInfo* __restrict__ mbs, uint4* __restrict__ rec,
                                                  int* __restrict__ row_lastq) {
@@ -82,8 +85,8 @@ __global__ __launch_bounds__(256) void k_db_prep(Geometry g, const FrameState* _
         if (mby > 0) t = mbs[i - g.mb_w];
         uint32_t v[4], h[4];
         for (int e = 0; e < 4; ++e) {
-            v[e] = db_edge_bs4(q, mbx > 0 ? &l : nullptr, e, true);
-            h[e] = db_edge_bs4(q, mby > 0 ? &t : nullptr, e, false);
+            v[e] = db_edge_bs4<kQuad>(q, mbx > 0 ? &l : nullptr, e, true);
+            h[e] = db_edge_bs4<kQuad>(q, mby > 0 ? &t : nullptr, e, false);
         }
         const bool dq = !fs->idr && carries_dqp(q);
         uint4 r;
@@ -847,9 +850,9 @@ std::vector<unsigned long long> deblock_row_stamps(int mb_h) {
 }
 
 void launch_deblock(const Geometry& g, const DeviceBuffers& b, const uint8_t* src_y, const uint8_t* src_uv,
-                    hipStream_t stream) {
+                    hipStream_t stream, bool quads) {
     if (g.mb_w > kDbMaxW || g.mb_h > kMaxSlices) throw std::invalid_argument("launch_deblock: picture too large");
-    hipLaunchKernelGGL(k_db_prep, dim3(g.mb_h), dim3(256), 0, stream, g, b.fs, b.mb, b.db_rec, b.db_rowq);
+    hipLaunchKernelGGL(quads ? k_db_prep<true> : k_db_prep<false>, dim3(g.mb_h), dim3(256), 0, stream, g, b.fs, b.mb, b.db_rec, b.db_rowq);
     DbGlobal G{b.db_glb, b.db_err, src_y, src_uv};
     static const int rows = [] {
         const char* e = std::getenv("MXDESK_DB_ROWS");

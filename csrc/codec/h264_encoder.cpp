@@ -422,7 +422,7 @@ void GpuH264Encoder::launcher_loop() {
         try {
             FrameSlot& sl = slots_[j.slot];
             HIP_CHECK(hipStreamWaitEvent(j.stream, sl.analysis_done, 0));
-            launch_entropy(geom_, sl.buf, sl.host_out, j.stream, j.sse_ready, sl.scroll.hint);
+            launch_entropy(geom_, sl.buf, sl.host_out, j.stream, j.sse_ready, sl.scroll.hint, cfg_.partitions >= 2);
             HIP_CHECK(hipGetLastError());
             HIP_CHECK(hipEventRecord(sl.done, j.stream));
         } catch (...) {
@@ -506,6 +506,7 @@ void GpuH264Encoder::enqueue_analysis_kernels(bool idr, const uint8_t* src_y, co
         // scroll hint: the probe pass goes before the search on the search's stream and is then the
         // picture's first kernel (it publishes the state and stamps the start)
         const ScrollBuffers* scroll = sl.scroll.reach ? &sl.scroll : nullptr;
+        const bool quads = cfg_.partitions >= 2;  // P_8x8 searched and coded: the kernels' _q8 instantiations
         if (side_me) {
             HIP_CHECK(hipStreamWaitEvent(stream_m_, ev_hpu_, 0));
             if (in_ev_) {
@@ -513,20 +514,20 @@ void GpuH264Encoder::enqueue_analysis_kernels(bool idr, const uint8_t* src_y, co
                 in_ev_ = nullptr;  // the analysis stream waits for the search, so for the input too
             }
             if (scroll) launch_scroll_probe(geom_, sl.buf, *scroll, src_y, stream_m_, pub);
-            launch_me(geom_, sl.buf, src_y, stream_m_, pub, true, scroll);
+            launch_me(geom_, sl.buf, src_y, stream_m_, pub, true, scroll, quads);
             HIP_CHECK(hipEventRecord(sl.me_done, stream_m_));
             HIP_CHECK(hipStreamWaitEvent(stream_, sl.me_done, 0));
-            launch_inter(geom_, sl.buf, src_y, src_uv, stream_);
+            launch_inter(geom_, sl.buf, src_y, src_uv, stream_, quads);
         } else if (!sl.me_unf && geom_.mb_w * geom_.mb_h <= kFusedMaxMbs) {
             // the search reads the picture the coder predicts from: one kernel searches and codes
             wait_input();
             if (scroll) launch_scroll_probe(geom_, sl.buf, *scroll, src_y, stream_, pub);
-            launch_p_fused(geom_, sl.buf, src_y, src_uv, stream_, pub, scroll);
+            launch_p_fused(geom_, sl.buf, src_y, src_uv, stream_, pub, scroll, quads);
         } else {
             wait_input();
             if (scroll) launch_scroll_probe(geom_, sl.buf, *scroll, src_y, stream_, pub);
-            launch_me(geom_, sl.buf, src_y, stream_, pub, false, scroll);
-            launch_inter(geom_, sl.buf, src_y, src_uv, stream_);
+            launch_me(geom_, sl.buf, src_y, stream_, pub, false, scroll, quads);
+            launch_inter(geom_, sl.buf, src_y, src_uv, stream_, quads);
         }
         if (cfg_.intra_in_p) launch_intra_in_p(geom_, sl.buf, src_y, src_uv, stream_);
     }
@@ -543,7 +544,7 @@ void GpuH264Encoder::link_entropy() {
 void GpuH264Encoder::enqueue_entropy() {
     drain_launcher();
     FrameSlot& sl = slots_[prep_slot_];
-    launch_entropy(geom_, sl.buf, sl.host_out, stream_e_ ? stream_e_ : stream_, nullptr, sl.scroll.hint);
+    launch_entropy(geom_, sl.buf, sl.host_out, stream_e_ ? stream_e_ : stream_, nullptr, sl.scroll.hint, cfg_.partitions >= 2);
 }
 
 void GpuH264Encoder::unfiltered_copy(FrameSlot& sl) {
@@ -562,7 +563,7 @@ void GpuH264Encoder::enqueue_kernels(bool idr, const uint8_t* src_y, const uint8
         hipEvent_t sse_ready = nullptr;
         if (sl.deblock) {
             unfiltered_copy(sl);
-            launch_deblock(geom_, sl.buf, src_y, src_uv, stream_);
+            launch_deblock(geom_, sl.buf, src_y, src_uv, stream_, cfg_.partitions >= 2);
             HIP_CHECK(hipEventRecord(sl.deblock_done, stream_));
             sse_ready = sl.deblock_done;
         }
@@ -586,13 +587,13 @@ void GpuH264Encoder::enqueue_kernels(bool idr, const uint8_t* src_y, const uint8
     if (sl.deblock) {  // in-loop filter on the analysis stream: the next frame predicts from it,
                          // while this frame's CAVLC runs beside it on the entropy stream
         unfiltered_copy(sl);
-        launch_deblock(geom_, sl.buf, src_y, src_uv, stream_);
+        launch_deblock(geom_, sl.buf, src_y, src_uv, stream_, cfg_.partitions >= 2);
         if (stream_e_) {
             HIP_CHECK(hipEventRecord(sl.deblock_done, stream_));
             sse_ready = sl.deblock_done;
         }
     }
-    launch_entropy(geom_, sl.buf, sl.host_out, es, sse_ready, sl.scroll.hint);
+    launch_entropy(geom_, sl.buf, sl.host_out, es, sse_ready, sl.scroll.hint, cfg_.partitions >= 2);
     HIP_CHECK(hipGetLastError());
 }
 
@@ -620,7 +621,7 @@ void GpuH264Encoder::fill_state(FrameSlot& sl, bool idr, int qp, int ref, int cu
     f.log2_max_frame_num = common_.log2_max_frame_num();
     f.aq = cfg_.aq;
     f.intra_in_p = cfg_.intra_in_p;
-    f.partitions = cfg_.partitions ? 1 : 0;
+    f.partitions = cfg_.partitions <= 0 ? 0 : (cfg_.partitions >= 2 ? 2 : 1);
     f.mask_mx0 = mask_mb_[0];
     f.mask_my0 = mask_mb_[1];
     f.mask_mx1 = mask_mb_[2];

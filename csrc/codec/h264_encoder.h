@@ -71,7 +71,9 @@ struct EncoderConfig {
     // throughput, profiles/r06_vp8db/NOTES.md; vp8_encoder.h LfDecision)
     int deblock = -1;
     // P pictures: also search 16x8 / 8x16 partitionings (two vectors per macroblock) and take one
-    // when its SAD + lambda * vector rate beats the 16x16 vector's
+    // when its SAD + lambda * vector rate beats the 16x16 vector's.  2: P_8x8 as well, one vector per
+    // 8x8 quadrant (four P_L0_8x8 sub-macroblocks), taken when strictly cheaper than the other shapes;
+    // the streams of 0 and 1 do not depend on it
     int partitions = 1;
     // a copy with aq < 0 resolved to the codec's default (each encoder keeps one as cfg_)
     EncoderConfig with_aq_default(int def) const {
@@ -457,10 +459,11 @@ void me_search_cpu(const uint8_t* sy, int pitch, const uint8_t* ref_y, int cw, i
                    int search_range, int subpel, int* mvx, int* mvy, int coarse, int gx = 0, int gy = 0,
                    uint8_t* path = nullptr);
 // The same search plus 16x8 / 8x16 partitionings (k_me_full with FrameState::partitions): writes
-// m.mvx / mvy (best 16x16 vector), m.part and m.pmv.
+// m.mvx / mvy (best 16x16 vector), m.part and m.pmv.  quads (partitions 2): P_8x8 too, whose four
+// vectors replace the 16x16 one (h264_gpu.h MbInfo).
 void me_search_parts_cpu(const uint8_t* sy, int pitch, const uint8_t* ref_y, int cw, int ch, int x0, int y0, int qp,
                          int search_range, int subpel, int coarse, MbInfo& m, int gx = 0, int gy = 0,
-                         uint8_t* path = nullptr);
+                         uint8_t* path = nullptr, bool quads = false);
 // The scroll probe pass of a P picture (the rules of k_scroll_probe): votes of the lattice's probe
 // macroblocks into hist (scroll_bins(D) zeroed bins, cleared again on return) and the decision.
 void scroll_probe_cpu(const uint8_t* sy, int pitch, const uint8_t* ref_y, int cw, int ch, int mb_w, int mb_h, int qp,

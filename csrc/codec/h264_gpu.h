@@ -15,6 +15,7 @@
 // Only the slice payloads (RBSP, byte aligned) leave the GPU; the host adds start
 // codes, NAL headers and emulation-prevention bytes (h264_encoder.cpp).
 #pragma once
+#include <cstddef>
 #include <vector>
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -25,6 +26,9 @@ namespace mx {
 namespace h264 {
 
 constexpr int kSlotWords = 640;   // per-MB CAVLC bit slot (2560 B >= worst case)
+// (the header of a P_8x8 macroblock, the longest of a P macroblock: ue(3), four ue(0), eight se() of at
+// most 29 bits for vector differences within +-2^13 quarter samples, coded_block_pattern, mb_qp_delta:
+// under 270 bits of the 20,480 here and of the 768 of a role's buffer, k_cavlc's kRoleWords)
 constexpr int kCoefStride = 416;  // int16 coefficients per MB
 constexpr int kCoefLuma = 0;      // [16 blkIdx][16 scan]
 constexpr int kCoefLumaDc = 256;  // [16 scan]
@@ -50,13 +54,24 @@ struct MbInfo {
     uint32_t cost;     // P pictures: inter luma SATD cost (+ mv rate), for the intra decision
     // inter partitioning (H.264 P pictures): part 0 = P_L0_16x16 (vector mvx / mvy), 1 = 16x8,
     // 2 = 8x16 with the vectors of partitions 0 / 1 in pmv[0..1] / pmv[2..3] (quarter-pel).
-    // mvx / mvy always keep the best 16x16 vector (the HEVC and VP8 encoders read only those).
+    // For part <= 2 mvx / mvy keep the best 16x16 vector (the HEVC and VP8 encoders, which run with
+    // partitions 0, read only those).
+    // part 3 = P_8x8, four P_L0_8x8 sub-macroblocks (EncoderConfig::partitions 2): the vectors of
+    // quadrants 0 TL, 1 TR, 2 BL, 3 BR are mvx / mvy, pmv[0..1], pmv[2..3] and pmv3[0..1].  Two more
+    // vectors do not fit the 7 spare bytes, so a P_8x8 macroblock keeps no 16x16 vector: its H.264
+    // readers -- blk_mv (h264_mb.h: prediction, coding, neighbours, the temporal class's zero_mv),
+    // inter_cost_mb, db_blk_mv and db_auto_count -- take the quadrants' vectors; pmv3 is only
+    // defined when part == 3.
     int16_t pmv[4];
     uint8_t part;
-    uint8_t pad_[7];
+    uint8_t pad0_;
+    int16_t pmv3[2];
+    uint8_t pad1_[2];
 };
 static_assert(sizeof(MbInfo) == 64, "MbInfo layout");
-enum MbPart : uint8_t { kPart16x16 = 0, kPart16x8 = 1, kPart8x16 = 2 };
+static_assert(offsetof(MbInfo, pmv) == 48 && offsetof(MbInfo, part) == 56 && offsetof(MbInfo, pmv3) == 58,
+              "MbInfo layout");
+enum MbPart : uint8_t { kPart16x16 = 0, kPart16x8 = 1, kPart8x16 = 2, kPart8x8 = 3 };  // = the mb_type written
 
 MXHD_GPU bool is_intra(const MbInfo& m) { return m.type != kMbP16x16; }
 // Whether macroblock (mbx, mby) is outside the quality-report mask of the frame state.
@@ -91,7 +106,7 @@ struct FrameState {
     int32_t log2_max_frame_num;
     int32_t aq;        // adaptive quantisation on/off (P frames)
     int32_t intra_in_p;  // P frames: k_intra_analyze / k_intra_wave run (distortion deltas included)
-    int32_t partitions;  // P frames: k_me_full also searches 16x8 / 8x16 partitionings (H.264)
+    int32_t partitions;  // P frames: k_me_full also searches 16x8 / 8x16 partitionings (H.264); 2: and P_8x8
     // quality report: MBs in [mask_mx0, mask_mx1) x [mask_my0, mask_my1) are left out of the 4th
     // distortion channel (e.g. the synthetic desktop's noise panel); empty rect = no mask
     int32_t mask_mx0, mask_my0, mask_mx1, mask_my1;
@@ -193,8 +208,12 @@ struct ScrollBuffers {
 // scroll: launch_scroll_probe went before on this stream -- it was the picture's first kernel and
 // stamped the start -- and the search may centre on scroll->hint (an instantiation of its own:
 // without the hint the kernels are what they were).
+// quads: FrameState::partitions is 2 -- the search also keeps a best per 8x8 quadrant and may decide
+// P_8x8 (again instantiations of their own, the _q8 kernels; launch_inter and launch_p_fused take the
+// same flag for the coder, which then predicts from up to four vectors).
 void launch_me(const Geometry& g, const DeviceBuffers& b, const uint8_t* src_y, hipStream_t stream,
-               const FrameState* publish = nullptr, bool side = false, const ScrollBuffers* scroll = nullptr);
+               const FrameState* publish = nullptr, bool side = false, const ScrollBuffers* scroll = nullptr,
+               bool quads = false);
 // The scroll probe pass of a P picture: votes of the lattice's probe macroblocks (k_scroll_probe) and
 // the decision into sb.hint (k_scroll_decide).  The picture's first kernel: `publish` as
 // launch_me.  Reads the source and the reference the search reads.
@@ -207,7 +226,7 @@ void launch_copy_luma(const Geometry& g, const uint8_t* luma, uint8_t* dst, hipS
 // from a reference picture on the device, by k_inter_encode's interpolation; out: 256 bytes
 void launch_mc_luma_test(const Geometry& g, const uint8_t* ref, int x4, int y4, uint8_t* out, hipStream_t stream);
 void launch_inter(const Geometry& g, const DeviceBuffers& b, const uint8_t* src_y, const uint8_t* src_uv,
-                  hipStream_t stream);
+                  hipStream_t stream, bool quads = false);
 // launch_me + launch_inter as one kernel (k_p_fused): a workgroup per macroblock searches, then codes
 // it on one wave.  For a P picture whose search reads the picture the coder predicts from
 // (FrameState::me_ref null); `publish` as launch_me.  The encoder uses it up to kFusedMaxMbs
@@ -217,7 +236,8 @@ void launch_inter(const Geometry& g, const DeviceBuffers& b, const uint8_t* src_
 // profiles/p_fused/NOTES.md).
 constexpr int kFusedMaxMbs = 8160;
 void launch_p_fused(const Geometry& g, const DeviceBuffers& b, const uint8_t* src_y, const uint8_t* src_uv,
-                    hipStream_t stream, const FrameState* publish = nullptr, const ScrollBuffers* scroll = nullptr);
+                    hipStream_t stream, const FrameState* publish = nullptr, const ScrollBuffers* scroll = nullptr,
+                    bool quads = false);
 // The first kernel of a frame (launch_intra for I, launch_me / launch_p_fused for P) publishes the frame
 // state: with `publish` non-null it takes the state by value and stores it to b.fs for the
 // later kernels (no copy node); with nullptr it reads b.fs (filled by a memcpy node, hipGraph).
@@ -232,16 +252,18 @@ void launch_hpel(const Geometry& g, const DeviceBuffers& b, uint8_t* const plane
 // diagnostics: device wall-clock (start, end) of every row wave of the last k_deblock, luma rows
 // then chroma rows
 std::vector<unsigned long long> deblock_row_stamps(int mb_h);
+// quads: the picture may hold P_8x8 macroblocks (launch_me): the strengths come from k_db_prep<true>
 void launch_deblock(const Geometry& g, const DeviceBuffers& b, const uint8_t* src_y, const uint8_t* src_uv,
-                    hipStream_t stream);
+                    hipStream_t stream, bool quads = false);
 // Copy the source luma into FrameState::save_src (IDR pictures; the pointer is read on the device
 // so a captured graph stays valid while the buffers alternate).
 void launch_save_src(const Geometry& g, const DeviceBuffers& b, const uint8_t* src_y, hipStream_t stream);
 // wait_for_sse: event the stream waits on after k_cavlc, before the distortion partials are
 // reduced (the deblocking kernels' completion on the analysis stream), or nullptr
 // scroll_hint: the P picture's hint (ScrollBuffers::hint) for OutHeader::scroll_dx / dy, or nullptr
+// quads: the picture may hold P_8x8 macroblocks (launch_me): k_cavlc<true> writes their sub_mb_pred syntax
 void launch_entropy(const Geometry& g, const DeviceBuffers& b, uint8_t* host_out, hipStream_t stream,
-                    hipEvent_t wait_for_sse = nullptr, const int32_t* scroll_hint = nullptr);
+                    hipEvent_t wait_for_sse = nullptr, const int32_t* scroll_hint = nullptr, bool quads = false);
 // P pictures, after launch_inter: open-loop intra analysis of every MB (intra vs inter) and the
 // closed-loop reconstruction of the MBs that switched to intra.
 void launch_intra_in_p(const Geometry& g, const DeviceBuffers& b, const uint8_t* src_y, const uint8_t* src_uv,

@@ -329,11 +329,12 @@ __device__ __forceinline__ unsigned long long me_neighbour(unsigned long long ce
 // this lane is lane `sub` of candidate k of vector pi and owns the 8 source samples at (xx, yy) of
 // the macroblock (srcw).  sp[pi]: the footprint staged around the integer match (vx, vy)[pi] on entry.
 // A step publishes its costs in cand (two barriers) and every thread takes the first lower cost in
-// subpel_offset order.
+// subpel_offset order.  on: false on a lane that owns no samples (an 8x8 quadrant fills 8 of the
+// group's 16 lanes); its (xx, yy) still has to lie inside the macroblock.
 template <int kN>
 __device__ __forceinline__ void me_refine(const uint8_t (*sp)[4][18][kSpW], uint32_t (*cand)[8], const uint32_t* srcw,
                                           int pi, int k, int sub, int xx, int yy, int lambda, int* vx, int* vy,
-                                          uint32_t* cost) {
+                                          uint32_t* cost, bool on = true) {
     const uint32_t s0 = srcw[yy * 4 + (xx >> 2)], s1 = srcw[yy * 4 + (xx >> 2) + 1];
     const int base_x4 = xx * 4 + 4 - vx[pi], base_y4 = yy * 4 + 4 - vy[pi];  // local qpel coords = base + candidate mv
     for (int step = 2; step >= 1; step >>= 1) {
@@ -345,6 +346,7 @@ __device__ __forceinline__ void me_refine(const uint8_t (*sp)[4][18][kSpW], uint
         for (int j = 0; j < 8; ++j) {
             d += abs(byte_of(j < 4 ? s0 : s1, j & 3) - qpel_lds(sp[pi], base_x4 + 4 * j + cx, base_y4 + cy));
         }
+        if (!on) d = 0;
         for (int o = kMeThreads / (16 * kN); o > 0; o >>= 1) d += __shfl_xor(d, o, 64);
         __syncthreads();  // the previous step's readers are done with cand
         if (sub == 0) cand[pi][k] = me_cost((uint32_t)d, lambda, cx, cy);
@@ -396,6 +398,23 @@ __device__ __forceinline__ MbInfo store_motion(MbInfo* __restrict__ mbs, int mbi
     const int none[2] = {0, 0};
     return store_motion(mbs, mbi, tid, cx, cy, mvx, mvy, kPart16x16, none, none);
 }
+// The same for a P_8x8 macroblock: the vectors of quadrants TL, TR, BL, BR (h264_gpu.h MbInfo).
+__device__ __forceinline__ MbInfo store_motion_quads(MbInfo* __restrict__ mbs, int mbi, int tid, int cx, int cy,
+                                                     const int (&qvx)[4], const int (&qvy)[4]) {
+    MbInfo out;
+    out.part = kPart8x8;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) set_quad_mv(out, q, 4 * cx + qvx[q], 4 * cy + qvy[q]);
+    if (tid == 0) {
+        MbInfo& m = mbs[mbi];
+        m.mvx = out.mvx;
+        m.mvy = out.mvy;
+        m.part = out.part;
+        for (int i = 0; i < 4; ++i) m.pmv[i] = out.pmv[i];
+        for (int i = 0; i < 2; ++i) m.pmv3[i] = out.pmv3[i];
+    }
+    return out;
+}
 // Returns the motion it stored in mbs[mbi] (mvx, mvy, part, pmv; the same on every thread): the
 // fused kernel codes the macroblock from it without reading it back.  win_lds: kWinWords of LDS.
 // kScroll (H.264 with EncoderConfig::scroll_range): a macroblock that fails the static exit looks at
@@ -403,7 +422,11 @@ __device__ __forceinline__ MbInfo store_motion(MbInfo* __restrict__ mbs, int mbi
 // window, candidates and footprints around the centre g instead of zero.  Vectors inside the body
 // stay local to the centre -- so does the rate term of me_cost -- and the centre is added to what
 // is stored.  Without kScroll the centre is the constant zero and the body is what it was.
-template <bool kScroll>
+// kQuad (H.264 with EncoderConfig::partitions 2; the state's partitions is then non-zero): every 8x8
+// quadrant keeps a running best of its own beside the halves', and the macroblock becomes P_8x8 --
+// four vectors, pmv3 stored and returned as well -- when that is strictly cheaper than the three
+// other shapes (me_search_parts_cpu has the rules).  Without kQuad the body is what it was.
+template <bool kScroll, bool kQuad = false>
 __device__ __forceinline__ MbInfo me_full_body(const Geometry& g, const MeState& st, const uint8_t* __restrict__ src_y,
                                                MbInfo* __restrict__ mbs, uint32_t* win_lds,
                                                const int32_t* __restrict__ hint = nullptr) {
@@ -529,7 +552,10 @@ __device__ __forceinline__ MbInfo me_full_body(const Geometry& g, const MeState&
     // partitions: per candidate the SAD of each 8x8 quadrant (TL, TR, BL, BR); the 16x16 key is
     // their sum (so the 16x16 decision is unchanged) and shapes T / B / L / R keep their own best
     unsigned long long pb[4] = {~0ull, ~0ull, ~0ull, ~0ull};
+    unsigned long long qb[4] = {~0ull, ~0ull, ~0ull, ~0ull};  // kQuad: quadrants TL, TR, BL, BR
     auto visit_quads = [&](const uint32_t* qd, int dxr, int dyr) {
+        if constexpr (kQuad)
+            for (int i = 0; i < 4; ++i) qb[i] = kmin(qb[i], mkey(qd[i], dxr, dyr));
         best = kmin(best, mkey(qd[0] + qd[1] + qd[2] + qd[3], dxr, dyr));
         pb[0] = kmin(pb[0], mkey(qd[0] + qd[1], dxr, dyr));
         pb[1] = kmin(pb[1], mkey(qd[2] + qd[3], dxr, dyr));
@@ -577,11 +603,26 @@ __device__ __forceinline__ MbInfo me_full_body(const Geometry& g, const MeState&
             if (lane == 0) pred4[sh][tid >> 6] = v;
         }
     }
+    __shared__ unsigned long long qred4[kQuad ? 4 : 1][kMeWaves];  // kQuad: [quadrant][wave]
+    if constexpr (kQuad) {
+        if (parts) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const unsigned long long v = wave_min_u64(qb[i]);
+                if (lane == 0) qred4[i][tid >> 6] = v;
+            }
+        }
+    }
     __syncthreads();
     unsigned long long b = block_min(red);
     unsigned long long pbest[4] = {~0ull, ~0ull, ~0ull, ~0ull};
     if (parts)
         for (int sh = 0; sh < 4; ++sh) pbest[sh] = block_min(pred4[sh]);
+    unsigned long long qbest[4] = {~0ull, ~0ull, ~0ull, ~0ull};
+    if constexpr (kQuad) {
+        if (parts)
+            for (int i = 0; i < 4; ++i) qbest[i] = block_min(qred4[i]);
+    }
     const uint8_t* wb = reinterpret_cast<const uint8_t*>(win32);
     const uint8_t* sb = reinterpret_cast<const uint8_t*>(srcw);
     if (parts && coarse) {
@@ -605,6 +646,24 @@ __device__ __forceinline__ MbInfo me_full_body(const Geometry& g, const MeState&
         __syncthreads();
         for (int s2 = 0; s2 < 4; ++s2)
             for (int i = 0; i < 8; ++i) pbest[s2] = kmin(pbest[s2], pnkey[s2][i]);
+        if constexpr (kQuad) {
+            // ... and of each quadrant's: 32 (quadrant, neighbour) pairs of 64-sample squares, a row
+            // of 8 samples per lane
+            __shared__ unsigned long long qnkey[4][8];
+            const int qi = ev >> 3;
+            const unsigned long long qk = me_neighbour<8>(qbest[qi], k, side, [&](int nxr, int nyr) {
+                const int rr = 8 * (qi >> 1) + sub, c0 = 8 * (qi & 1);
+                int d = 0;
+#pragma unroll
+                for (int j = 0; j < 8; ++j)
+                    d += abs((int)sb[rr * 16 + c0 + j] - (int)wb[(nyr + rr) * kWinStride + nxr + c0 + j]);
+                return d;
+            }, mkey);
+            if (sub == 0) qnkey[qi][k] = qk;
+            __syncthreads();
+            for (int s2 = 0; s2 < 4; ++s2)
+                for (int i = 0; i < 8; ++i) qbest[s2] = kmin(qbest[s2], qnkey[s2][i]);
+        }
     }
     if (coarse) {  // the 8 integer neighbours of the grid best: one per 32-lane group, 8 samples per lane
         __shared__ unsigned long long nkey[8];
@@ -631,6 +690,38 @@ __device__ __forceinline__ MbInfo me_full_body(const Geometry& g, const MeState&
         const uint32_t chz = (uint32_t)(pbest[0] >> 32) + (uint32_t)(pbest[1] >> 32) + 2u * (uint32_t)lambda;
         const uint32_t cvt = (uint32_t)(pbest[2] >> 32) + (uint32_t)(pbest[3] >> 32) + 2u * (uint32_t)lambda;
         const int part = (c16 <= chz && c16 <= cvt) ? kPart16x16 : (chz <= cvt ? kPart16x8 : kPart8x16);
+        if constexpr (kQuad) {
+            // P_8x8 only when strictly cheaper than all three: four costs + 8 lambda (mb_type ue(3)
+            // and four sub_mb_type ue(0), 9 bits against the 1 of 16x16 -- the "+ 2 lambda" accounting)
+            const uint32_t c8 = (uint32_t)(qbest[0] >> 32) + (uint32_t)(qbest[1] >> 32) + (uint32_t)(qbest[2] >> 32) +
+                                (uint32_t)(qbest[3] >> 32) + 8u * (uint32_t)lambda;
+            if (c8 < c16 && c8 < chz && c8 < cvt) {  // uniform
+                int qvx[4], qvy[4];
+                uint32_t qcost[4];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const int cb = (int)(qbest[i] & 0xffff);
+                    qvx[i] = 4 * ((cb % side) - R);
+                    qvy[i] = 4 * ((cb / side) - R);
+                    qcost[i] = (uint32_t)(qbest[i] >> 32);
+                }
+                if (st.subpel) {
+                    // per quadrant over its own square, quadrants {0, 1} then {2, 3} through the two
+                    // footprints: 16 lanes per candidate as for the halves, 8 of them hold a row
+                    __shared__ uint32_t qcand[2][8];
+                    const int pi = tid >> 7, k = (tid >> 4) & 7, sub = tid & 15;
+#pragma unroll
+                    for (int pass = 0; pass < 2; ++pass) {
+                        build_footprints(reinterpret_cast<const uint8_t*>(win_lds), fp_org(qvx[2 * pass], qvy[2 * pass]),
+                                         fp_org(qvx[2 * pass + 1], qvy[2 * pass + 1]), 2, sp2, fp_b1, tid);
+                        __syncthreads();
+                        me_refine<2>(sp2, qcand, srcw, pi, k, sub, 8 * pi, 8 * pass + (sub & 7), lambda, qvx + 2 * pass,
+                                     qvy + 2 * pass, qcost + 2 * pass, sub < 8);
+                    }
+                }
+                return store_motion_quads(mbs, mbi, tid, cx, cy, qvx, qvy);
+            }
+        }
         if (part != kPart16x16) {
             const int s0 = part == kPart16x8 ? 0 : 2;  // pbest index of partition 0
             int pvx[2], pvy[2];
@@ -706,6 +797,39 @@ __global__ __launch_bounds__(kMeThreads) void k_me_full_val_scroll(Geometry g, S
     __shared__ uint32_t win_lds[kWinWords];
     publish_state(sa);
     me_full_body<true>(g, me_state(sa.v), src_y, mbs, win_lds, hint);
+}
+// The four again with the 8x8 quadrants searched (EncoderConfig::partitions 2): kernels of their own,
+// so that the ones above keep their registers and occupancy (profiles/p8x8/NOTES.md).  Entry points
+// written out like the four above: one shared templated entry point changed the instructions of
+// k_me_full and k_me_full_scroll.
+__global__ __launch_bounds__(kMeThreads) void k_me_full_q8(Geometry g, StateArg sa, const uint8_t* __restrict__ src_y,
+                                                           MbInfo* __restrict__ mbs) {
+    __shared__ uint32_t win_lds[kWinWords];
+    publish_state(sa);
+    me_full_body<false, true>(g, sa.publish ? me_state(sa.v) : me_state(*sa.dst), src_y, mbs, win_lds);
+}
+__global__ __launch_bounds__(kMeThreads) void k_me_full_val_q8(Geometry g, StateArg sa,
+                                                               const uint8_t* __restrict__ src_y,
+                                                               MbInfo* __restrict__ mbs) {
+    __shared__ uint32_t win_lds[kWinWords];
+    publish_state(sa);
+    me_full_body<false, true>(g, me_state(sa.v), src_y, mbs, win_lds);
+}
+__global__ __launch_bounds__(kMeThreads) void k_me_full_scroll_q8(Geometry g, StateArg sa,
+                                                                  const uint8_t* __restrict__ src_y,
+                                                                  MbInfo* __restrict__ mbs,
+                                                                  const int32_t* __restrict__ hint) {
+    __shared__ uint32_t win_lds[kWinWords];
+    publish_state(sa);
+    me_full_body<true, true>(g, sa.publish ? me_state(sa.v) : me_state(*sa.dst), src_y, mbs, win_lds, hint);
+}
+__global__ __launch_bounds__(kMeThreads) void k_me_full_val_scroll_q8(Geometry g, StateArg sa,
+                                                                      const uint8_t* __restrict__ src_y,
+                                                                      MbInfo* __restrict__ mbs,
+                                                                      const int32_t* __restrict__ hint) {
+    __shared__ uint32_t win_lds[kWinWords];
+    publish_state(sa);
+    me_full_body<true, true>(g, me_state(sa.v), src_y, mbs, win_lds, hint);
 }
 
 // ------------------------------------------------------------------ scroll probe
@@ -1049,6 +1173,9 @@ struct InterLds {
 // (mvx / mvy / part / pmv), residual, transforms or their shortcuts, reconstruction, the rest of
 // MbInfo and the macroblock's distortion (mb_sse[c * nmb + mbi], c = Y, U, V: k_scan_rows sums
 // them).  L is the wave's own; it synchronises with wave_lds_sync() only.
+// kQuad: the macroblock may be P_8x8 (part 3, four vectors: pmv3 is read too).  Without it part is
+// at most 2 and the vector lookups leave the quadrant case out: the coder is then what it was.
+template <bool kQuad = false>
 __device__ __forceinline__ void inter_code_mb(const Geometry& g, const CodeState& fs, const uint8_t* __restrict__ src_y,
                                               const uint8_t* __restrict__ src_uv, MbInfo* __restrict__ mbs,
                                               int16_t* __restrict__ coef, uint32_t* __restrict__ mb_sse, int mbi,
@@ -1059,6 +1186,10 @@ __device__ __forceinline__ void inter_code_mb(const Geometry& g, const CodeState
     mi.mvy = (int16_t)__builtin_amdgcn_readfirstlane((int)motion.mvy);
     mi.part = (uint8_t)__builtin_amdgcn_readfirstlane((int)motion.part);
     for (int i = 0; i < 4; ++i) mi.pmv[i] = (int16_t)__builtin_amdgcn_readfirstlane((int)motion.pmv[i]);
+    if constexpr (kQuad) {
+        for (int i = 0; i < 2; ++i)
+            mi.pmv3[i] = mi.part == kPart8x8 ? (int16_t)__builtin_amdgcn_readfirstlane((int)motion.pmv3[i]) : (int16_t)0;
+    }
     const int nmb = g.mb_w * g.mb_h;
     const int mbx = mbi % g.mb_w, mby = mbi / g.mb_w;
     const int x0 = mbx * 16, y0 = mby * 16;
@@ -1075,7 +1206,7 @@ __device__ __forceinline__ void inter_code_mb(const Geometry& g, const CodeState
     int cpv[2] = {0, 0}, crs[2] = {0, 0};
     {
         const int r = lane >> 2, c0 = (lane & 3) * 4;
-        const Mv lv = px_mv(mi, c0, r);  // the lane's 4 luma samples lie in one partition
+        const Mv lv = px_mv<kQuad>(mi, c0, r);  // the lane's 4 luma samples lie in one partition
         mvx = lv.x;
         mvy = lv.y;
         sw = *reinterpret_cast<const uint32_t*>(src_y + (y0 + r) * g.pitch + x0 + c0);
@@ -1102,10 +1233,38 @@ __device__ __forceinline__ void inter_code_mb(const Geometry& g, const CodeState
         // luma prediction from the reference picture; the macroblock's one or two vectors are
         // uniform across the wave (the lane's 4 samples lie in partition lpi: vector (mvx, mvy))
         const int part = __builtin_amdgcn_readfirstlane((int)mi.part);
-        const Mv va = blk_mv(mi, 0, 0), vb = blk_mv(mi, part == kPart8x16 ? 2 : 0, part == kPart16x8 ? 2 : 0);
+        const Mv va = blk_mv<kQuad>(mi, 0, 0), vb = blk_mv<kQuad>(mi, part == kPart8x16 ? 2 : 0, part == kPart16x8 ? 2 : 0);
         const int vax = __builtin_amdgcn_readfirstlane(va.x), vay = __builtin_amdgcn_readfirstlane(va.y);
         const int vbx = __builtin_amdgcn_readfirstlane(vb.x), vby = __builtin_amdgcn_readfirstlane(vb.y);
-        if ((vax | vay | vbx | vby) & 3) {
+        bool quad_mc = false;
+        if constexpr (kQuad) {
+            if (part == kPart8x8) {
+                // four vectors, some fractional: the two-window staging twice, quadrants {0, 1} then
+                // {2, 3}; a lane's samples lie in quadrant 2 * (r >> 3) + (c0 >> 3).  All full-sample:
+                // the lane's own vector below, as for the other shapes (va = vb = quadrant 0's there).
+                int qx[4], qy[4], any = 0;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const Mv v = quad_mv(mi, q);
+                    qx[q] = v.x;  // mi is wave-uniform already
+                    qy[q] = v.y;
+                    any |= qx[q] | qy[q];
+                }
+                if (any & 3) {
+                    uint32_t ptop = 0, pbot = 0;
+                    mc_luma_wave(L.mcw, ref_y, g.pitch, g.coded_w, g.coded_h, 2, x0 * 4 + qx[0], y0 * 4 + qy[0],
+                                 x0 * 4 + qx[1], y0 * 4 + qy[1], lane, c0 >> 3, &ptop);
+                    wave_lds_sync();  // every lane has read the first pair's windows
+                    mc_luma_wave(L.mcw, ref_y, g.pitch, g.coded_w, g.coded_h, 2, x0 * 4 + qx[2], y0 * 4 + qy[2],
+                                 x0 * 4 + qx[3], y0 * 4 + qy[3], lane, c0 >> 3, &pbot);
+                    pw = r < 8 ? ptop : pbot;
+                    quad_mc = true;
+                }
+            }
+        }
+        if (quad_mc) {
+            // pw is the prediction
+        } else if ((vax | vay | vbx | vby) & 3) {
             // a fractional vector: interpolated from the block's window(s) staged in LDS
             const int lpi = part == kPart16x8 ? (r >> 3) : (part == kPart8x16 ? (c0 >> 3) : 0);
             mc_luma_wave(L.mcw, ref_y, g.pitch, g.coded_w, g.coded_h, part == kPart16x16 ? 1 : 2, x0 * 4 + vax,
@@ -1126,7 +1285,7 @@ __device__ __forceinline__ void inter_code_mb(const Geometry& g, const CodeState
         lsad = (int)__builtin_amdgcn_sad_u8(sw, pw, 0u);
         const int cr_ = lane >> 3, cc = lane & 7;
         const int xc = x0 / 2 + cc, yc = y0 / 2 + cr_;
-        const Mv cv = px_mv(mi, 2 * cc, 2 * cr_);
+        const Mv cv = px_mv<kQuad>(mi, 2 * cc, 2 * cr_);
         for (int comp = 0; comp < 2; ++comp) {
             cpv[comp] = chroma_pred8(ref_uv, g.pitch, cw, ch, comp, xc * 8 + cv.x, yc * 8 + cv.y);
             crs[comp] = (int)src_uv[yc * g.pitch + 2 * xc + comp] - cpv[comp];
@@ -1346,7 +1505,7 @@ __device__ __forceinline__ void inter_code_mb(const Geometry& g, const CodeState
         m.qp = (uint8_t)qp;
         m.i16_mode = 0;
         m.chroma_mode = 0;
-        m.cost = want_cost ? inter_cost_mb(satd_mb, fs.qp, mi) : 0u;
+        m.cost = want_cost ? inter_cost_mb<kQuad>(satd_mb, fs.qp, mi) : 0u;
     }
 }
 
@@ -1364,6 +1523,20 @@ __global__ __launch_bounds__(256) void k_inter_encode(Geometry g, const FrameSta
     if (mbi >= g.mb_w * g.mb_h) return;  // the whole wave
     const MbInfo mi = mbs[mbi];
     inter_code_mb(g, code_state(*fs), src_y, src_uv, mbs, coef, mb_sse, mbi, lane, mi, lds[wave]);
+}
+// The same for a picture that may hold P_8x8 macroblocks (EncoderConfig::partitions 2)
+__global__ __launch_bounds__(256) void k_inter_encode_q8(Geometry g, const FrameState* __restrict__ fs,
+                                                          const uint8_t* __restrict__ src_y,
+                                                          const uint8_t* __restrict__ src_uv, MbInfo* __restrict__ mbs,
+                                                          int16_t* __restrict__ coef, uint32_t* __restrict__ mb_sse,
+                                                          int* __restrict__ wave_prog) {
+    __shared__ InterLds lds[4];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int mbi = blockIdx.x * 4 + wave;
+    if (blockIdx.x == 0 && threadIdx.x == 0) wave_prog[1] = 0;  // k_intra_analyze's candidate list (next kernel)
+    if (mbi >= g.mb_w * g.mb_h) return;  // the whole wave
+    const MbInfo mi = mbs[mbi];
+    inter_code_mb<true>(g, code_state(*fs), src_y, src_uv, mbs, coef, mb_sse, mbi, lane, mi, lds[wave]);
 }
 
 // One kernel per P picture whose search reads the picture the coder predicts from: a workgroup per
@@ -1404,6 +1577,40 @@ __global__ __launch_bounds__(kMeThreads) __attribute__((amdgpu_waves_per_eu(6)))
     if (threadIdx.x >= 64) return;
     inter_code_mb(g, cs, src_y, src_uv, mbs, coef, mb_sse, blockIdx.x, threadIdx.x, mi,
                   *reinterpret_cast<InterLds*>(win_lds));
+}
+// k_p_fused and k_p_fused_scroll with the 8x8 quadrants searched and P_8x8 coded
+// (EncoderConfig::partitions 2): kernels of their own, as the scroll ones are.  5 waves per SIMD asked
+// for: the eight extra running bests need ~100 registers; at 6 waves the spills cost more than the
+// occupancy returns and left alone the allocation ends at 4 (1080p desktop: 78.5 / 69.6 / 74.1 us for
+// 6 / 5 / no limit, profiles/p8x8/NOTES.md)
+template <bool kScroll>
+__device__ __forceinline__ void p_fused_q8_body(const Geometry& g, const StateArg& sa, const uint8_t* __restrict__ src_y,
+                                                const uint8_t* __restrict__ src_uv, MbInfo* __restrict__ mbs,
+                                                int16_t* __restrict__ coef, uint32_t* __restrict__ mb_sse,
+                                                int* __restrict__ wave_prog, const int32_t* __restrict__ hint,
+                                                uint32_t* win_lds) {
+    publish_state(sa);
+    if (blockIdx.x == 0 && threadIdx.x == 0) wave_prog[1] = 0;  // k_intra_analyze's candidate list (next kernel)
+    const MeState st = sa.publish ? me_state(sa.v) : me_state(*sa.dst);
+    const CodeState cs = sa.publish ? code_state(sa.v) : code_state(*sa.dst);
+    const MbInfo mi = me_full_body<kScroll, true>(g, st, src_y, mbs, win_lds, hint);  // the same on every thread
+    __syncthreads();  // every wave is done with the window
+    if (threadIdx.x >= 64) return;
+    inter_code_mb<true>(g, cs, src_y, src_uv, mbs, coef, mb_sse, blockIdx.x, threadIdx.x, mi,
+                        *reinterpret_cast<InterLds*>(win_lds));
+}
+__global__ __launch_bounds__(kMeThreads) __attribute__((amdgpu_waves_per_eu(5))) void k_p_fused_q8(
+    Geometry g, StateArg sa, const uint8_t* __restrict__ src_y, const uint8_t* __restrict__ src_uv,
+    MbInfo* __restrict__ mbs, int16_t* __restrict__ coef, uint32_t* __restrict__ mb_sse, int* __restrict__ wave_prog) {
+    __shared__ uint32_t win_lds[kWinWords];
+    p_fused_q8_body<false>(g, sa, src_y, src_uv, mbs, coef, mb_sse, wave_prog, nullptr, win_lds);
+}
+__global__ __launch_bounds__(kMeThreads) __attribute__((amdgpu_waves_per_eu(5))) void k_p_fused_scroll_q8(
+    Geometry g, StateArg sa, const uint8_t* __restrict__ src_y, const uint8_t* __restrict__ src_uv,
+    MbInfo* __restrict__ mbs, int16_t* __restrict__ coef, uint32_t* __restrict__ mb_sse, int* __restrict__ wave_prog,
+    const int32_t* __restrict__ hint) {
+    __shared__ uint32_t win_lds[kWinWords];
+    p_fused_q8_body<true>(g, sa, src_y, src_uv, mbs, coef, mb_sse, wave_prog, hint, win_lds);
 }
 
 // ------------------------------------------------------------------ intra analysis
@@ -2339,6 +2546,9 @@ __device__ __forceinline__ uint32_t role_get(const uint32_t* buf, uint32_t b, in
 // wave no longer idles 36 of its 64 lanes; the prefix sum, ballots and word assembly are
 // segmented per half.
 constexpr int kCavlcMbPerBlock = 8;
+// kQuad: the picture may hold P_8x8 macroblocks (EncoderConfig::partitions 2).  A template kernel: behind a
+// shared device function k_cavlc<false> did not compile to the instructions k_cavlc had.
+template <bool kQuad>
 __global__ __launch_bounds__(256) void k_cavlc(Geometry g, const FrameState* __restrict__ fs, MbInfo* __restrict__ mbs,
                                                const int16_t* __restrict__ coef, uint32_t* __restrict__ slot,
                                                uint32_t* __restrict__ slot_bits) {
@@ -2373,8 +2583,8 @@ __global__ __launch_bounds__(256) void k_cavlc(Geometry g, const FrameState* __r
     const int16_t* mc = coef + (size_t)mbi * kCoefStride;
 
     // motion vector prediction + P_Skip decision (every lane computes the same values)
-    int mvd[4];
-    const bool skip = decide_skip(nb, av, mvd);
+    int mvd[kQuad ? 8 : 4];
+    const bool skip = decide_skip<kQuad>(nb, av, mvd);
     // mb_qp_delta: QP predictor = QP of the previous MB in the slice that carried one (a P
     // macroblock with residual); skipped / residual-free MBs inherit it.  Half-wave-parallel
     // backward search (the ballot holds active lanes only; this half's bits are taken), 512 MBs
@@ -2425,7 +2635,7 @@ __global__ __launch_bounds__(256) void k_cavlc(Geometry g, const FrameState* __r
     if (!skip && lane < kNumRoles) {
         BitWriter w;
         w.init(rbuf[wave][lane]);
-        code_role(w, lane, g, fs->idr, nb, cbuf[wave], av, mvd, dqp);
+        code_role<kQuad>(w, lane, g, fs->idr, nb, cbuf[wave], av, mvd, dqp);
         w.flush();
         bits = w.bits;
     }
@@ -2493,6 +2703,8 @@ __device__ __forceinline__ SliceParams slice_params(const FrameState* fs, int s,
 // unit bits of the row excluding the skip-run prefix of its first coded MB (that run depends
 // on earlier rows)}; and this row's share of the distortion partials.
 // slot_bits[i]: 0 = P_Skip, 0xffffffff = slot overflow, else coded MB bits (>= 1).
+// (kQuad: as k_cavlc -- the adaptive filter's class counts have a rule for P_8x8 macroblocks)
+template <bool kQuad>
 __global__ __launch_bounds__(kScanThreads) void k_scan_rows(Geometry g, const FrameState* __restrict__ fs,
                                                             const uint32_t* __restrict__ slot_bits,
                                                             uint4* __restrict__ row_agg,
@@ -2572,7 +2784,7 @@ __global__ __launch_bounds__(kScanThreads) void k_scan_rows(Geometry g, const Fr
     if (idr || !db_cnt) return;
     // adaptive in-loop filter: this row's temporal-class counts (h264_deblock.h db_auto_count)
     DbAutoCounts ac;
-    for (int j = t; j < g.mb_w; j += kScanThreads) db_auto_count(mbs, g.mb_w, base + j, ac);
+    for (int j = t; j < g.mb_w; j += kScanThreads) db_auto_count<kQuad>(mbs, g.mb_w, base + j, ac);
     uint32_t cv[3] = {ac.coherent, ac.changed, ac.moving};
     __shared__ uint32_t cred[3][kScanThreads / 64];
     for (int c = 0; c < 3; ++c) {
@@ -2950,22 +3162,23 @@ void launch_mc_luma_test(const Geometry& g, const uint8_t* ref, int x4, int y4, 
 }
 
 void launch_me(const Geometry& g, const DeviceBuffers& b, const uint8_t* src_y, hipStream_t stream,
-               const FrameState* publish, bool side, const ScrollBuffers* scroll) {
+               const FrameState* publish, bool side, const ScrollBuffers* scroll, bool quads) {
     const int nmb = g.mb_w * g.mb_h;
     const StateArg sa = make_state_arg(b, publish, !scroll);  // H.264: a P picture's first kernel, or k_scroll_probe was
     if (scroll) {
         if (side && publish)
-            hipLaunchKernelGGL(k_me_full_val_scroll, dim3(nmb), dim3(kMeThreads), 0, stream, g, sa, src_y, b.mb,
-                               scroll->hint);
+            hipLaunchKernelGGL(quads ? k_me_full_val_scroll_q8 : k_me_full_val_scroll, dim3(nmb), dim3(kMeThreads), 0,
+                               stream, g, sa, src_y, b.mb, scroll->hint);
         else
-            hipLaunchKernelGGL(k_me_full_scroll, dim3(nmb), dim3(kMeThreads), 0, stream, g, sa, src_y, b.mb,
-                               scroll->hint);
+            hipLaunchKernelGGL(quads ? k_me_full_scroll_q8 : k_me_full_scroll, dim3(nmb), dim3(kMeThreads), 0, stream, g,
+                               sa, src_y, b.mb, scroll->hint);
         return;
     }
     if (side && publish)
-        hipLaunchKernelGGL(k_me_full_val, dim3(nmb), dim3(kMeThreads), 0, stream, g, sa, src_y, b.mb);
+        hipLaunchKernelGGL(quads ? k_me_full_val_q8 : k_me_full_val, dim3(nmb), dim3(kMeThreads), 0, stream, g, sa,
+                           src_y, b.mb);
     else
-        hipLaunchKernelGGL(k_me_full, dim3(nmb), dim3(kMeThreads), 0, stream, g, sa, src_y, b.mb);
+        hipLaunchKernelGGL(quads ? k_me_full_q8 : k_me_full, dim3(nmb), dim3(kMeThreads), 0, stream, g, sa, src_y, b.mb);
 }
 
 void launch_scroll_probe(const Geometry& g, const DeviceBuffers& b, const ScrollBuffers& sb, const uint8_t* src_y,
@@ -2977,21 +3190,21 @@ void launch_scroll_probe(const Geometry& g, const DeviceBuffers& b, const Scroll
 }
 
 void launch_inter(const Geometry& g, const DeviceBuffers& b, const uint8_t* src_y, const uint8_t* src_uv,
-                  hipStream_t stream) {
+                  hipStream_t stream, bool quads) {
     const int nmb = g.mb_w * g.mb_h;
-    hipLaunchKernelGGL(k_inter_encode, dim3((nmb + 3) / 4), dim3(256), 0, stream, g, b.fs, src_y, src_uv, b.mb,
+    hipLaunchKernelGGL(quads ? k_inter_encode_q8 : k_inter_encode, dim3((nmb + 3) / 4), dim3(256), 0, stream, g, b.fs, src_y, src_uv, b.mb,
                        b.coef, b.mb_sse, b.wave_prog);
 }
 
 void launch_p_fused(const Geometry& g, const DeviceBuffers& b, const uint8_t* src_y, const uint8_t* src_uv,
-                    hipStream_t stream, const FrameState* publish, const ScrollBuffers* scroll) {
+                    hipStream_t stream, const FrameState* publish, const ScrollBuffers* scroll, bool quads) {
     const int nmb = g.mb_w * g.mb_h;
     const StateArg sa = make_state_arg(b, publish, !scroll);
     if (scroll)
-        hipLaunchKernelGGL(k_p_fused_scroll, dim3(nmb), dim3(kMeThreads), 0, stream, g, sa, src_y, src_uv, b.mb, b.coef,
+        hipLaunchKernelGGL(quads ? k_p_fused_scroll_q8 : k_p_fused_scroll, dim3(nmb), dim3(kMeThreads), 0, stream, g, sa, src_y, src_uv, b.mb, b.coef,
                            b.mb_sse, b.wave_prog, scroll->hint);
     else
-        hipLaunchKernelGGL(k_p_fused, dim3(nmb), dim3(kMeThreads), 0, stream, g, sa, src_y, src_uv, b.mb, b.coef,
+        hipLaunchKernelGGL(quads ? k_p_fused_q8 : k_p_fused, dim3(nmb), dim3(kMeThreads), 0, stream, g, sa, src_y, src_uv, b.mb, b.coef,
                            b.mb_sse, b.wave_prog);
 }
 
@@ -3039,15 +3252,15 @@ void launch_save_src(const Geometry& g, const DeviceBuffers& b, const uint8_t* s
 }
 
 void launch_entropy(const Geometry& g, const DeviceBuffers& b, uint8_t* host_out, hipStream_t stream,
-                    hipEvent_t wait_for_sse, const int32_t* scroll_hint) {
+                    hipEvent_t wait_for_sse, const int32_t* scroll_hint, bool quads) {
     const int nmb = g.mb_w * g.mb_h;
-    hipLaunchKernelGGL(k_cavlc, dim3((nmb + kCavlcMbPerBlock - 1) / kCavlcMbPerBlock), dim3(256), 0, stream, g, b.fs,
+    hipLaunchKernelGGL(quads ? k_cavlc<true> : k_cavlc<false>, dim3((nmb + kCavlcMbPerBlock - 1) / kCavlcMbPerBlock), dim3(256), 0, stream, g, b.fs,
                        b.mb, b.coef, b.slot,
                        b.slot_bits);
     if (wait_for_sse) HIP_CHECK(hipStreamWaitEvent(stream, wait_for_sse, 0));
     if (g.mb_h > kScanMaxRows || g.mb_w > kScanThreads * kScanRowPer)
         throw std::runtime_error("launch_entropy: frame too large for the row scan");
-    hipLaunchKernelGGL(k_scan_rows, dim3(g.mb_h), dim3(kScanThreads), 0, stream, g, b.fs, b.slot_bits, b.row_agg,
+    hipLaunchKernelGGL(quads ? k_scan_rows<true> : k_scan_rows<false>, dim3(g.mb_h), dim3(kScanThreads), 0, stream, g, b.fs, b.slot_bits, b.row_agg,
                        b.row_sse, b.mb, b.db_cnt, b.mb_sse);
     hipLaunchKernelGGL(k_scan_out, dim3(g.mb_h), dim3(kScanThreads), 0, stream, g, b.fs, b.slot_bits, b.row_agg,
                        b.row_sse, b.coded_info, b.slice_info, b.out_bytes, b.out_hdr, b.quad_unit, b.db_cnt, scroll_hint);

@@ -48,16 +48,40 @@ MXHD MbNbrs mb_nbrs(const MbInfo* mbs, int mbi, int mb_w) {
     return MbNbrs{&mbs[mbi], &mbs[mbi - 1], &mbs[mbi - mb_w], &mbs[mbi - mb_w + 1], &mbs[mbi - mb_w - 1]};
 }
 
-// Vector of 4x4 block (bx, by) of an inter macroblock (partition-aware).
+// Vector of 4x4 block (bx, by) of an inter macroblock (partition-aware).  kQuad false: the caller
+// knows that the macroblock is not P_8x8 (a coder kernel of a picture searched without quadrants).
+template <bool kQuad = true>
 MXHD Mv blk_mv(const MbInfo& m, int bx, int by) {
     if (m.part == kPart16x8) return by < 2 ? Mv{m.pmv[0], m.pmv[1]} : Mv{m.pmv[2], m.pmv[3]};
     if (m.part == kPart8x16) return bx < 2 ? Mv{m.pmv[0], m.pmv[1]} : Mv{m.pmv[2], m.pmv[3]};
+    if (kQuad && m.part == kPart8x8) {  // quadrant 0 TL, 1 TR, 2 BL, 3 BR (the layout: h264_gpu.h MbInfo)
+        // the four vectors read first, then chosen by value (a choice between the fields' addresses
+        // would keep the whole MbInfo in scratch memory on the GPU)
+        const int x0 = m.mvx, y0 = m.mvy, x1 = m.pmv[0], y1 = m.pmv[1], x2 = m.pmv[2], y2 = m.pmv[3], x3 = m.pmv3[0], y3 = m.pmv3[1];
+        const bool right = bx >= 2, low = by >= 2;
+        return Mv{low ? (right ? x3 : x2) : (right ? x1 : x0), low ? (right ? y3 : y2) : (right ? y1 : y0)};
+    }
     return Mv{m.mvx, m.mvy};
 }
+// Vector of quadrant q of a P_8x8 macroblock, and storing it.
+MXHD Mv quad_mv(const MbInfo& m, int q) { return blk_mv(m, 2 * (q & 1), q & 2); }
+MXHD void set_quad_mv(MbInfo& m, int q, int vx, int vy) {
+    if (q == 0) {
+        m.mvx = (int16_t)vx;
+        m.mvy = (int16_t)vy;
+    } else {
+        int16_t* p = q == 3 ? m.pmv3 : m.pmv + 2 * (q - 1);
+        p[0] = (int16_t)vx;
+        p[1] = (int16_t)vy;
+    }
+}
 // Vector of luma sample (x, y) of the macroblock.
-MXHD Mv px_mv(const MbInfo& m, int x, int y) { return blk_mv(m, x >> 2, y >> 2); }
+template <bool kQuad = true>
+MXHD Mv px_mv(const MbInfo& m, int x, int y) { return blk_mv<kQuad>(m, x >> 2, y >> 2); }
 
-// Neighbour for motion-vector prediction: block (bx, by) of macroblock p.
+// Neighbour for motion-vector prediction: block (bx, by) of macroblock p.  (kQuad through the
+// functions below: as blk_mv -- false where no macroblock of the picture is P_8x8, k_cavlc.)
+template <bool kQuad = true>
 MXHD MvNb mv_nb_blk(const MbInfo* p, bool avail, int bx, int by) {
     MvNb n;
     n.avail = avail;
@@ -67,7 +91,7 @@ MXHD MvNb mv_nb_blk(const MbInfo* p, bool avail, int bx, int by) {
     const MbInfo& m = *p;
     if (m.type == kMbP16x16) {
         n.ref = 0;
-        n.mv = blk_mv(m, bx, by);
+        n.mv = blk_mv<kQuad>(m, bx, by);
     }
     return n;
 }
@@ -75,6 +99,7 @@ MXHD MvNb mv_nb_blk(const MbInfo* p, bool avail, int bx, int by) {
 // 8.4.1.3 prediction of partition `idx` (0 / 1) of a 16x8 / 8x16 macroblock: neighbours A, B, C
 // of the partition (C replaced by D when unavailable; blocks of the right neighbour are never
 // available yet), the directional rules, else the median.  mv0: this MB's partition 0 vector.
+template <bool kQuad = true>
 MXHD Mv predict_mv_part(const MbNbrs& nb, const Avail& av, int part, int idx, Mv mv0) {
     MvNb own;
     own.avail = true;
@@ -83,52 +108,101 @@ MXHD Mv predict_mv_part(const MbNbrs& nb, const Avail& av, int part, int idx, Mv
     MvNb a, b, c;
     if (part == kPart16x8) {
         if (idx == 0) {
-            a = mv_nb_blk(nb.left, av.left, 3, 0);
-            b = mv_nb_blk(nb.top, av.top, 0, 3);
-            c = av.topright ? mv_nb_blk(nb.topright, true, 0, 3) : mv_nb_blk(nb.topleft, av.topleft, 3, 3);
+            a = mv_nb_blk<kQuad>(nb.left, av.left, 3, 0);
+            b = mv_nb_blk<kQuad>(nb.top, av.top, 0, 3);
+            c = av.topright ? mv_nb_blk<kQuad>(nb.topright, true, 0, 3) : mv_nb_blk<kQuad>(nb.topleft, av.topleft, 3, 3);
             if (b.ref == 0) return b.mv;
         } else {
-            a = mv_nb_blk(nb.left, av.left, 3, 2);
+            a = mv_nb_blk<kQuad>(nb.left, av.left, 3, 2);
             b = own;
-            c = mv_nb_blk(nb.left, av.left, 3, 1);  // C = (16, 7) not yet decoded -> D = (-1, 7)
+            c = mv_nb_blk<kQuad>(nb.left, av.left, 3, 1);  // C = (16, 7) not yet decoded -> D = (-1, 7)
             if (a.ref == 0) return a.mv;
         }
     } else {
         if (idx == 0) {
-            a = mv_nb_blk(nb.left, av.left, 3, 0);
-            b = mv_nb_blk(nb.top, av.top, 0, 3);
-            c = av.top ? mv_nb_blk(nb.top, true, 2, 3) : mv_nb_blk(nb.topleft, av.topleft, 3, 3);
+            a = mv_nb_blk<kQuad>(nb.left, av.left, 3, 0);
+            b = mv_nb_blk<kQuad>(nb.top, av.top, 0, 3);
+            c = av.top ? mv_nb_blk<kQuad>(nb.top, true, 2, 3) : mv_nb_blk<kQuad>(nb.topleft, av.topleft, 3, 3);
             if (a.ref == 0) return a.mv;
         } else {
             a = own;
-            b = mv_nb_blk(nb.top, av.top, 2, 3);
-            c = av.topright ? mv_nb_blk(nb.topright, true, 0, 3) : mv_nb_blk(nb.top, av.top, 1, 3);
+            b = mv_nb_blk<kQuad>(nb.top, av.top, 2, 3);
+            c = av.topright ? mv_nb_blk<kQuad>(nb.topright, true, 0, 3) : mv_nb_blk<kQuad>(nb.top, av.top, 1, 3);
             if (c.ref == 0) return c.mv;
         }
     }
     return predict_mv16x16(a, b, c);
 }
 
-// P_Skip decision + the motion vector differences of a P macroblock: mvd[0..1] (16x16 or
-// partition 0), mvd[2..3] (partition 1).  Returns true for P_Skip (16x16 only).
+// 8.4.1.3 prediction of quadrant q (0 TL, 1 TR, 2 BL, 3 BR) of a P_8x8 macroblock: the plain median
+// of neighbours A, B, C (C replaced by D when unavailable), no directional rule.  The quadrants
+// before q are this macroblock's own (read through blk_mv: they are final when q is predicted).
+//   q | A              | B              | C, and D when C is unavailable
+//   0 | left MB (3, 0) | top MB (0, 3)  | top MB (2, 3); top-left MB (3, 3) when the top is unavailable
+//   1 | quadrant 0     | top MB (2, 3)  | top-right MB (0, 3); else top MB (1, 3)
+//   2 | left MB (3, 2) | quadrant 0     | quadrant 1
+//   3 | quadrant 2     | quadrant 1     | not yet decoded -> quadrant 0
+MXHD Mv predict_mv_quad(const MbNbrs& nb, const Avail& av, int q) {
+    auto own = [&](int k) {
+        MvNb n;
+        n.avail = true;
+        n.ref = 0;
+        n.mv = quad_mv(*nb.self, k);
+        return n;
+    };
+    MvNb a, b, c;
+    if (q == 0) {
+        a = mv_nb_blk(nb.left, av.left, 3, 0);
+        b = mv_nb_blk(nb.top, av.top, 0, 3);
+        c = av.top ? mv_nb_blk(nb.top, true, 2, 3) : mv_nb_blk(nb.topleft, av.topleft, 3, 3);
+    } else if (q == 1) {
+        a = own(0);
+        b = mv_nb_blk(nb.top, av.top, 2, 3);
+        c = av.topright ? mv_nb_blk(nb.topright, true, 0, 3) : mv_nb_blk(nb.top, av.top, 1, 3);
+    } else if (q == 2) {
+        a = mv_nb_blk(nb.left, av.left, 3, 2);
+        b = own(0);
+        c = own(1);
+    } else {
+        a = own(2);
+        b = own(1);
+        c = own(0);
+    }
+    return predict_mv16x16(a, b, c);
+}
+
+// P_Skip decision + the motion vector differences of a P macroblock: mvd[0..1] (16x16, partition 0
+// or quadrant 0), mvd[2..3] (partition 1 or quadrant 1), mvd[4..7] (quadrants 2, 3).  Returns true
+// for P_Skip (16x16 only).
+// kQuad false: mvd has four entries.
+template <bool kQuad = true>
 MXHD bool decide_skip(const MbNbrs& nb, const Avail& av, int* mvd) {
     const MbInfo& m = *nb.self;
     mvd[0] = mvd[1] = mvd[2] = mvd[3] = 0;
+    if (kQuad) mvd[4] = mvd[5] = mvd[6] = mvd[7] = 0;
     if (m.type != kMbP16x16) return false;
+    if (kQuad && m.part == kPart8x8) {
+        for (int q = 0; q < 4; ++q) {
+            const Mv v = quad_mv(m, q), p = predict_mv_quad(nb, av, q);
+            mvd[2 * q] = v.x - p.x;
+            mvd[2 * q + 1] = v.y - p.y;
+        }
+        return false;
+    }
     if (m.part != kPart16x16) {
         const Mv v0{m.pmv[0], m.pmv[1]}, v1{m.pmv[2], m.pmv[3]};
-        const Mv p0 = predict_mv_part(nb, av, m.part, 0, v0);
-        const Mv p1 = predict_mv_part(nb, av, m.part, 1, v0);
+        const Mv p0 = predict_mv_part<kQuad>(nb, av, m.part, 0, v0);
+        const Mv p1 = predict_mv_part<kQuad>(nb, av, m.part, 1, v0);
         mvd[0] = v0.x - p0.x;
         mvd[1] = v0.y - p0.y;
         mvd[2] = v1.x - p1.x;
         mvd[3] = v1.y - p1.y;
         return false;
     }
-    const MvNb a = mv_nb_blk(nb.left, av.left, 3, 0);
-    const MvNb b = mv_nb_blk(nb.top, av.top, 0, 3);
-    MvNb c = mv_nb_blk(nb.topright, av.topright, 0, 3);
-    if (!av.topright) c = mv_nb_blk(nb.topleft, av.topleft, 3, 3);
+    const MvNb a = mv_nb_blk<kQuad>(nb.left, av.left, 3, 0);
+    const MvNb b = mv_nb_blk<kQuad>(nb.top, av.top, 0, 3);
+    MvNb c = mv_nb_blk<kQuad>(nb.topright, av.topright, 0, 3);
+    if (!av.topright) c = mv_nb_blk<kQuad>(nb.topleft, av.topleft, 3, 3);
     const Mv pskip = predict_mv_skip(a, b, c);
     const Mv p = predict_mv16x16(a, b, c);
     mvd[0] = m.mvx - p.x;
@@ -136,7 +210,7 @@ MXHD bool decide_skip(const MbNbrs& nb, const Avail& av, int* mvd) {
     return m.cbp == 0 && m.mvx == pskip.x && m.mvy == pskip.y;
 }
 
-template <class W>
+template <bool kQuad = true, class W>
 MXHD void code_role(W& w, int role, const Geometry& g, int idr, const MbNbrs& nb, const int16_t* mc,
                     const Avail& av, const int* mvd, int dqp = 0) {
     const MbInfo& m = *nb.self;
@@ -176,13 +250,17 @@ MXHD void code_role(W& w, int role, const Geometry& g, int idr, const MbNbrs& nb
             put_ue(w, (uint32_t)cbp_to_codenum(cbp, true));
             if (cbp) put_se(w, dqp);
         } else {
-            put_ue(w, m.part);  // P_L0_16x16 / P_L0_L0_16x8 / P_L0_L0_8x16 (one reference: no ref_idx)
+            put_ue(w, m.part);  // P_L0_16x16 / P_L0_L0_16x8 / P_L0_L0_8x16 / P_8x8 (one reference: no ref_idx)
+            if (kQuad && m.part == kPart8x8)
+                for (int q = 0; q < 4; ++q) put_ue(w, 0u);  // sub_mb_type P_L0_8x8
             put_se(w, mvd[0]);
             put_se(w, mvd[1]);
             if (m.part != kPart16x16) {
                 put_se(w, mvd[2]);
                 put_se(w, mvd[3]);
             }
+            if (kQuad && m.part == kPart8x8)
+                for (int i = 4; i < 8; ++i) put_se(w, mvd[i]);
             put_ue(w, (uint32_t)cbp_to_codenum(cbp, false));
             if (cbp) put_se(w, dqp);  // mb_qp_delta (adaptive quantisation)
         }
@@ -320,9 +398,19 @@ MXHD bool drop_chroma_for(int aq, int tclass, bool luma_dropped) {
 MXHD uint32_t inter_cost(uint32_t satd, int frame_qp, int mvx, int mvy) {
     return satd + (uint32_t)(lambda_sad(frame_qp) * (mvd_bits(mvx) + mvd_bits(mvy)));
 }
-// ... of a partitioned macroblock: both vectors' rate
+// ... of a partitioned macroblock: both vectors' rate, or all four (kQuad: as blk_mv)
+template <bool kQuad = true>
 MXHD uint32_t inter_cost_mb(uint32_t satd, int frame_qp, const MbInfo& m) {
     if (m.part == kPart16x16) return inter_cost(satd, frame_qp, m.mvx, m.mvy);
+    if (kQuad && m.part == kPart8x8) {  // all eight components
+        int bits = 0;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const Mv v = quad_mv(m, q);
+            bits += mvd_bits(v.x) + mvd_bits(v.y);
+        }
+        return satd + (uint32_t)(lambda_sad(frame_qp) * bits);
+    }
     return satd + (uint32_t)(lambda_sad(frame_qp) *
                              (mvd_bits(m.pmv[0]) + mvd_bits(m.pmv[1]) + mvd_bits(m.pmv[2]) + mvd_bits(m.pmv[3])));
 }

@@ -413,7 +413,7 @@ class Decoder:
         self.cur = None
         self.mbs: list[MbState] = []
         self.slice_count = 0
-        self.stats = {"skip": 0, "i16": 0, "i4": 0, "p": 0, "pcm": 0}
+        self.stats = {"skip": 0, "i16": 0, "i4": 0, "p": 0, "pcm": 0, "p8x8": 0}  # p8x8: those of "p" coded P_8x8
 
     # ------------------------------------------------------------------ top level
     def decode(self, stream: bytes) -> list[tuple[np.ndarray, np.ndarray, np.ndarray]]:
@@ -1356,9 +1356,16 @@ class Decoder:
         self.cur = (Yp[4:, 4:], Cp[0][2:, 2:], Cp[1][2:, 2:])
 
     def decode_inter_mb(self, r, addr, sid, mb_type, x0, y0):
-        if mb_type >= 3:
-            raise DecodeError("P_8x8 not supported")
-        nparts = 1 if mb_type == 0 else 2
+        if mb_type == 4:
+            raise DecodeError("mb_type P_8x8ref0 not supported")
+        if mb_type == 3:
+            # sub_mb_pred() (7.3.5.2): the four sub_mb_type first; only P_L0_8x8 (one vector per
+            # sub-macroblock) is decoded
+            for q in range(4):
+                sub = r.ue()
+                if sub != 0:
+                    raise DecodeError(f"sub_mb_type {sub} of sub-macroblock {q} not supported (only P_L0_8x8)")
+        nparts = 1 if mb_type == 0 else (4 if mb_type == 3 else 2)
         refs = []
         for _ in range(nparts):
             if self.num_ref > 1:
@@ -1371,8 +1378,13 @@ class Decoder:
             geo = [(0, 0, 16, 16, None)]
         elif mb_type == 1:
             geo = [(0, 0, 16, 8, "16x8_top"), (0, 8, 16, 8, "16x8_bot")]
-        else:
+        elif mb_type == 2:
             geo = [(0, 0, 8, 16, "8x16_left"), (8, 0, 8, 16, "8x16_right")]
+        else:
+            # sub-macroblocks in mbPartIdx order (6.4.2.1: raster over the 8x8 quadrants); their
+            # neighbours A, B, C / D come from 6.4.11.7 through _mvp's positions (x - 1, y),
+            # (x, y - 1), (x + 8, y - 1) / (x - 1, y - 1), the median of 8.4.1.3.1 without a directional rule
+            geo = [(8 * (q & 1), 8 * (q >> 1), 8, 8, None) for q in range(4)]
         cur_parts: dict = {}
         mvs = []
         for (px, py, w, h, shape) in geo:
@@ -1420,6 +1432,7 @@ class Decoder:
             self._recon_chroma(comp, addr, cpred[comp], chroma, qp)
         self.decoded_mbs += 1
         self.stats["p"] += 1
+        self.stats["p8x8"] += mb_type == 3
 
 
 # ----------------------------------------------------------------------------- deblocking (8.7)

@@ -199,13 +199,23 @@ class _Subscriber:
             pass  # loop closed
 
 
+def apply_encoder_args(enc, a: dict) -> None:
+    """The stream's encoder options into a native EncoderConfig (``SessionConfig.enc``)."""
+    enc.bitrate_kbps = a["bitrate_kbps"]
+    enc.keyint = a["keyint"]
+    enc.search_range = a["search_range"]
+    enc.scroll_range = a["scroll_range"]
+    enc.partitions = a["partitions"]  # H.264 (HEVC and VP8 code 16x16 units whatever it says)
+    enc.subpel = 1 if a["subpel"] else 0
+
+
 class StreamPipeline:
     def __init__(self, width: int, height: int, fps: int, *, backend: str = "gpu", device: int = 0,
                  bitrate_kbps: int = 8000, keyint: int = 0, search_range: int = 16, subpel: bool = True,
                  noise: bool = True, out_width: int = 0, out_height: int = 0, session_name: str = "0",
                  capture: Any = None, metrics: SessionMetrics | None = None, queue_frames: int | None = None,
                  stall_s: float = 2.0, paced: bool = True, codec: str = "h264",
-                 idr_min_interval_s: float | None = None, scroll_range: int = 0):
+                 idr_min_interval_s: float | None = None, scroll_range: int = 0, partitions: int = 1):
         if codec not in CODEC_IDS:
             raise ValueError(f"unknown codec {codec!r} (h264 | hevc | vp8)")
         self.codec = codec
@@ -224,7 +234,7 @@ class StreamPipeline:
         self.paced = paced
         self.bitrate_kbps = bitrate_kbps  # configured CBR target (congestion control upper bound)
         self._enc_args = dict(bitrate_kbps=bitrate_kbps, keyint=keyint, search_range=search_range, subpel=subpel,
-                              noise=noise, scroll_range=scroll_range)
+                              noise=noise, scroll_range=scroll_range, partitions=partitions)
         self.last_scroll = (0, 0)  # scroll hint of the last P picture (H.264 with scroll_range; /status)
         self._subs: list[_Subscriber] = []
         self._lock = threading.Lock()
@@ -272,11 +282,7 @@ class StreamPipeline:
             cfg.width, cfg.height, cfg.fps = self.width, self.height, self.fps
             cfg.out_width, cfg.out_height = self.out_w, self.out_h
             cfg.noise = 1 if a["noise"] else 0
-            cfg.enc.bitrate_kbps = a["bitrate_kbps"]
-            cfg.enc.keyint = a["keyint"]
-            cfg.enc.search_range = a["search_range"]
-            cfg.enc.scroll_range = a["scroll_range"]
-            cfg.enc.subpel = 1 if a["subpel"] else 0
+            apply_encoder_args(cfg.enc, a)
             cfg.codec = self.codec
             self._sess = N.Session(cfg)
             self._cpu = None

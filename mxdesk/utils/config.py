@@ -153,6 +153,8 @@ SCHEMA: list[Var] = [
     Var("search_range", ["MXDESK_SEARCH_RANGE"], 16, int, "motion search radius (integer pels, <= 32)"),
     Var("scroll_range", ["MXDESK_SCROLL_RANGE"], 0, int,
         "H.264: largest scroll (luma samples, <= 192) the P-picture probe pass looks for; 0 = off"),
+    Var("h264_partitions", ["MXDESK_H264_PARTITIONS"], 1, int,
+        "H.264 P macroblock shapes: 0 = 16x16 only, 1 = and 16x8 / 8x16, 2 = and P_8x8 (a vector per 8x8 quadrant)"),
     Var("subpel", ["MXDESK_SUBPEL"], True, bool, "quarter-pel motion refinement"),
     Var("noise", ["MXDESK_NOISE"], True, bool, "synthetic desktop: animated-noise panel"),
     Var("wall", ["MXDESK_WALL"], "", str, "tiled wall layout, e.g. '2x2' (one tile per GPU)"),
@@ -263,6 +265,8 @@ class Config:
             raise ValueError("MXDESK_SEARCH_RANGE must be in [1, 32]")
         if not 0 <= v["scroll_range"] <= 192:
             raise ValueError("MXDESK_SCROLL_RANGE must be in [0, 192]")
+        if v["h264_partitions"] not in (0, 1, 2):
+            raise ValueError("MXDESK_H264_PARTITIONS must be 0, 1 or 2")
         if v["source"] not in ("auto", "synthetic", "x11"):
             raise ValueError("MXDESK_SOURCE must be auto, synthetic or x11")
         self.encoder_backend  # noqa: B018  (raises on unknown encoders)
