@@ -422,7 +422,41 @@ PYBIND11_MODULE(_native, m) {
         .def("set_bitrate", [](vp8::GpuVp8Encoder& e, int k) { e.common().set_bitrate(k); })
         .def_property_readonly("stats", &vp8::GpuVp8Encoder::last_stats);
 
-    m.def("hevc_token_selftest", &hevc::token_selftest, py::arg("seed"), py::arg("slices"));
+    m.def("hevc_token_selftest", &hevc::token_selftest, py::arg("seed"), py::arg("slices"),
+          py::arg("intra_tu4") = false);
+    // the 4x4 DST-VII of intra luma TUs on (n, 4, 4) int32 blocks: forward (residual -> coefficients)
+    // or inverse (scaled coefficients -> residual), hevc_core.h fwd_dst4 / inv_dst4
+    m.def(
+        "hevc_dst4",
+        [](py::array_t<int32_t, py::array::c_style | py::array::forcecast> a, bool inverse) {
+            if (a.ndim() != 3 || a.shape(1) != 4 || a.shape(2) != 4) throw std::invalid_argument("blocks (n, 4, 4)");
+            py::array_t<int32_t> out({a.shape(0), (py::ssize_t)4, (py::ssize_t)4});
+            for (py::ssize_t i = 0; i < a.shape(0); ++i) {
+                if (inverse)
+                    hevc::inv_dst4(a.data() + 16 * i, out.mutable_data() + 16 * i);
+                else
+                    hevc::fwd_dst4(a.data() + 16 * i, out.mutable_data() + 16 * i);
+            }
+            return out;
+        },
+        py::arg("blocks"), py::arg("inverse") = false);
+    m.def("hevc_dst4_matrix", []() {
+        py::array_t<int32_t> t({4, 4});
+        for (int i = 0; i < 16; ++i) t.mutable_data()[i] = hevc::kDst4[i];
+        return t;
+    });
+    // intra modes whose N x N prediction never reads the below-left (hevc_core.h bl_safe_modes), and
+    // the closed form the 4x4 luma TUs use (intra_tu4_bl_safe), as bit masks
+    m.def("hevc_bl_safe_modes", [](int log2n, int cidx) { return hevc::bl_safe_modes(log2n, cidx); });
+    m.def("hevc_tu4_bl_safe_mask", []() {
+        uint64_t m = 0;
+        for (int mode = 0; mode < 35; ++mode) m |= (uint64_t)hevc::intra_tu4_bl_safe(mode) << mode;
+        return m;
+    });
+    // reference availability of 4x4 TU j of node k of a split intra unit (hevc_core.h split_tu4_avl)
+    m.def("hevc_split_tu4_avl", [](int k, int j, bool al, bool ac, bool at, bool atr, bool abl) {
+        return hevc::split_tu4_avl(k, j, al, ac, at, atr, abl);
+    });
     py::class_<hevc::CpuHevcEncoder>(m, "CpuHevcEncoder")
         .def(py::init<const h264::EncoderConfig&>())
         .def(
@@ -467,7 +501,9 @@ PYBIND11_MODULE(_native, m) {
                  for (const auto& c : e.cus()) t.push_back(c.type);
                  return t;
              })
-        .def("cu_info",  // (type, qp, cbf, tu_split, coding-tree depth, 4x4 luma node mask) per 16x16 unit
+        // (type, qp, cbf, tu_split, coding-tree depth, 4x4 luma node mask) per 16x16 unit; the mask
+        // (column 5) is set for inter units (tu_split 2) and, with hevc_intra_split 2, for intra units
+        .def("cu_info",
              [](hevc::CpuHevcEncoder& e) {
                  const auto& cus = e.cus();
                  py::array_t<int32_t> a({(py::ssize_t)cus.size(), (py::ssize_t)6});

@@ -100,7 +100,10 @@ struct EncoderConfig {
                               // 8x8 luma node again into four 4x4 TUs (2), per node by SSE + lambda * bits
     // HEVC I pictures: a 16x16 intra unit may code its transform tree as four 8x8 luma / 4x4 chroma TUs,
     // each predicted from the reconstruction of the TUs before it (same mode; mode-dependent scans),
-    // decided open-loop from the source (hevc_core.h intra_split_wins)
+    // decided open-loop from the source (hevc_core.h intra_split_wins).  2: each 8x8 luma node of such a
+    // unit may split again into four 4x4 luma TUs (DST-VII; the node's chroma stays one 4x4 TU per
+    // component), max_transform_hierarchy_depth_intra 2, decided per node open-loop as well (hevc_core.h
+    // intra_tu4_wins).  0 and 1 code the streams they always coded.
     int hevc_intra_split = 1;
     int hevc_slice_cost = 1536;  // HEVC without WPP: P-picture slice work target (hevc_core.h cu_cost units)
     // HEVC wavefront parallel processing (entropy_coding_sync_enabled_flag): P pictures in slices of

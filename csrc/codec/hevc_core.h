@@ -1730,7 +1730,10 @@ constexpr uint32_t kTokTerm = 255;
 constexpr int kTokBypassMax = 11;
 // Upper bound of the tokens of one CTU: 24 coded sub-blocks of at most 1 csbf + 16 sig + 8 gt1 +
 // 1 gt2 + 2 sign + 16 * 5 remaining (escape prefix, EGk prefix and suffix split at 11 bins), plus
-// the last-position, CU and SAO syntax.
+// the last-position, CU and SAO syntax.  Sixteen 4x4 luma TUs (inter tu4, or intra with tree depth 2,
+// whose levels are never decimated) keep the 24 sub-blocks and add, over the 256: 24 last positions of at
+// most 6 context bins + 2 suffix tokens, 16 + 4 cbf_luma, 4 x 3 child flags -- under 230 with the
+// largest head (an AMVP CU with SAO); an intra head is smaller.
 constexpr uint32_t kMaxCuTokens = 24 * 108 + 256;
 
 // Records bins as tokens (same interface as CabacEnc).  Consecutive bypass bins are merged.
@@ -2019,6 +2022,97 @@ MXHD bool intra_split_wins(int cost16, int cost8, int lambda) { return cost8 + l
 // search cannot win and is skipped (flat content; the decision is unchanged)
 MXHD bool intra_split_possible(int cost16, int lambda) { return cost16 > lambda * (kIntraSplitBits + 2); }
 
+// Second level (EncoderConfig::hevc_intra_split 2, max_transform_hierarchy_depth_intra 2): an 8x8
+// luma node of a split intra unit may split again into four 4x4 luma TUs (CuInfo::tu4 bit k, levels
+// in sub-blocks 4k + j), each predicted in the unit's mode -- nTbS 4: no reference smoothing; the DC
+// / mode 10 / mode 26 edge filters apply -- from the reconstruction of everything decoded before it
+// and transformed with DST-VII; the node's chroma stays one 4x4 TU per component, coded after the
+// fourth luma TU.
+// split_tu4_avl: reference availability (split_tu_avl's bits) of 4x4 TU j of node k, i.e. of the 4x4
+// block (gx, gy) of the unit.  Each reference segment lies in one 4x4 block: inside the unit that
+// block is there when it precedes (gx, gy) in z order (whether its node is one 8x8 TU or four 4x4
+// TUs), outside it follows the unit's left / corner / top / top-right and, for the rows below the
+// unit, abl: the unit's below-left.  The decoder has that one only in a CTB's first unit, where the
+// raster wavefront has not reconstructed it (bl_pending), so both encoders pass abl = false and such
+// a unit's node 2 goes 4x4 only in a mode that never reads it (intra_tu4_bl_safe).
+// own_node = false (the open-loop decision only): the TUs of the TU's own node count as absent too,
+// so that its references are those the whole node has (see intra_tu4_wins).
+MXHD int tu4_order(int gx, int gy) { return ((gy >> 1) << 3) | ((gx >> 1) << 2) | ((gy & 1) << 1) | (gx & 1); }
+MXHD int split_tu4_avl(int k, int j, bool al, bool ac, bool at, bool atr, bool abl, bool own_node = true) {
+    const int gx = (k & 1) * 2 + (j & 1), gy = (k >> 1) * 2 + (j >> 1), me = 4 * k + j;
+    auto there = [&](int nx, int ny) -> bool {
+        if (ny < 0) return nx < 0 ? ac : (nx < 4 ? at : atr);
+        if (nx < 0) return ny < 4 ? al : abl;
+        if (nx > 3 || ny > 3) return false;
+        return tu4_order(nx, ny) < (own_node ? me : 4 * k);
+    };
+    return (there(gx - 1, gy + 1) ? 1 : 0) | (there(gx - 1, gy) ? 2 : 0) | (there(gx - 1, gy - 1) ? 4 : 0) |
+           (there(gx, gy - 1) ? 8 : 0) | (there(gx + 1, gy - 1) ? 16 : 0);
+}
+// 4x4 luma modes that never read the below-left references (no smoothing at nTbS 4: DC, and the
+// angular modes from the horizontal one on; planar and modes 2..9 read them) = bl_safe_modes(2, 0)
+MXHD bool intra_tu4_bl_safe(int mode) { return mode == 1 || mode >= 10; }
+// Open-loop choice per 8x8 node of a unit whose split won, in the split tree's mode (no further mode
+// search): the node predicted from the source as four 4x4 TUs plus lambda * kIntraTu4Bits against the
+// node predicted as one 8x8 TU.  The four TUs take their references from outside the node only
+// (split_tu4_avl with own_node = false; missing ones are substituted): predicted from the *source* of
+// the TUs before them they would look perfect wherever the node's first TU takes the whole misprediction,
+// while in the coder that TU's coarse reconstruction is what the others are predicted from -- with that
+// chain the rule sent single window edges to 4x4 TUs and lost 1.65 % on the 320x192 desktop.
+// Each option is costed in the transform it
+// would use, as the sum of the absolute coefficients on the 4x4 Hadamard SATD's scale: the 8x8 one by
+// the 8x8 Hadamard transform of its residual (node_cost8_of), the 4x4 one by the DST-VII of its four
+// residual blocks (dst4_row_stage, node_cost4_of).  The 4x4 Hadamard SATD of both -- the first rule
+// tried -- counts a flat residual four times for the 8x8 TU, which codes it in one coefficient, and
+// once for the DST, which spreads it over sixteen: on the synthetic desktop it sent window edges to
+// 4x4 TUs and cost 9 .. 17 % BD-rate.  kIntraTu4Bits from a sweep on the CPU encoder; all in
+// profiles/hevc_intra4/NOTES.md.
+constexpr int kIntraTu4Bits = 16;
+MXHD bool intra_tu4_wins(int cost8, int cost4, int lambda) { return cost4 + lambda * kIntraTu4Bits < cost8; }
+// a node whose 8x8 cost is at most the flag cost cannot lose: its comparison is skipped (decision unchanged)
+MXHD bool intra_tu4_possible(int cost8, int lambda) { return cost8 > lambda * kIntraTu4Bits; }
+// sum |8x8 Hadamard coefficients| (gain 8) -> the 4x4 Hadamard's gain 4
+MXHD int node_cost8_of(int sum_abs) { return (sum_abs + 1) >> 1; }
+
+// DST-VII of 4x4 intra luma TUs (8.6.4.2 trType 1): row = frequency, column = sample; the stage
+// shifts of the 4x4 core transform (fwd_transform / inv_transform with log2n 2).
+constexpr int8_t kDst4[16] = {29, 55, 74, 84, 74, 74, 0, -74, 84, -29, -74, 55, 55, -84, 74, -29};
+// node_cost4 (the 4x4 option's cost): the DST's row stage rounded back to the residual's scale (the
+// matrix has gain 128; |value| <= 482, exact in f16 for the matrix cores), the column stage's sum of
+// absolute values (gain 128) -> gain 4
+MXHD int dst4_row_stage(int s) { return (s + 64) >> 7; }
+MXHD int node_cost4_of(int sum_abs) { return (sum_abs + 16) >> 5; }
+MXHD void fwd_dst4(const int* res, int* out) {
+    int tmp[16];
+    for (int y = 0; y < 4; ++y)
+        for (int k = 0; k < 4; ++k) {
+            int s = 0;
+            for (int n = 0; n < 4; ++n) s += kDst4[k * 4 + n] * res[y * 4 + n];
+            tmp[y * 4 + k] = (s + 1) >> 1;
+        }
+    for (int k2 = 0; k2 < 4; ++k2)
+        for (int k = 0; k < 4; ++k) {
+            int s = 0;
+            for (int y = 0; y < 4; ++y) s += kDst4[k2 * 4 + y] * tmp[y * 4 + k];
+            out[k2 * 4 + k] = (s + 128) >> 8;
+        }
+}
+MXHD void inv_dst4(const int* d, int* r) {
+    int g[16];
+    for (int x = 0; x < 4; ++x)
+        for (int y = 0; y < 4; ++y) {
+            int s = 0;
+            for (int k = 0; k < 4; ++k) s += kDst4[k * 4 + y] * d[k * 4 + x];
+            g[y * 4 + x] = clip16((s + 64) >> 7);
+        }
+    for (int y = 0; y < 4; ++y)
+        for (int x = 0; x < 4; ++x) {
+            int s = 0;
+            for (int k = 0; k < 4; ++k) s += kDst4[k * 4 + x] * g[y * 4 + k];
+            r[y * 4 + x] = (s + 2048) >> 12;
+        }
+}
+
 constexpr int kIntraCoarse[11] = {0, 1, 2, 6, 10, 14, 18, 22, 26, 30, 34};
 constexpr int kIntraNoMode = 0x7fffffff;
 template <class F>
@@ -2147,6 +2241,25 @@ MXHD int tu_encode(int log2n, const int* res, int qp, bool intra, int16_t* level
     if (log2n == 2) return tu_encode_t<2>(res, qp, intra, levels, rres, scan);
     if (log2n == 3) return tu_encode_t<3>(res, qp, intra, levels, rres, scan);
     return tu_encode_t<4>(res, qp, intra, levels, rres);
+}
+// A 4x4 intra luma TU: tu_encode(2, .., intra) with the DST-VII in place of the core transform
+// (intra rounding, no decimation, no trailing trim), levels in `scan` order.
+MXHD int tu4_intra_encode(const int* res, int qp, int16_t* levels, int* rres, int scan) {
+    int c[16], d[16];
+    fwd_dst4(res, c);
+    int nz = 0;
+    for (int v = 0; v < 4; ++v)
+        for (int u = 0; u < 4; ++u) {
+            const int l = quant_coef(c[v * 4 + u], qp, 2, true);
+            levels[scan_index_s(2, scan, u, v)] = (int16_t)l;
+            nz += l != 0;
+            d[v * 4 + u] = dequant_coef(l, qp, 2);
+        }
+    if (nz)
+        inv_dst4(d, rres);
+    else
+        for (int i = 0; i < 16; ++i) rres[i] = 0;
+    return nz;
 }
 
 // lambda for SSE decisions, HM's 0.57 * 2^((QP-12)/3), in 1/16 units (integer: CPU == GPU)

@@ -431,6 +431,56 @@ int satd16(const uint8_t* sy, int pitch, int x0, int y0, const int* pred) {
     return satd;
 }
 
+// Costs of the 8x8 node at (bx, by) of the unit for the 4x4-versus-8x8 choice, each in the transform
+// the option would use and on the 4x4 Hadamard SATD's scale (4 x the orthonormal coefficients):
+// node_cost8: 8x8 Hadamard SATD of the node's residual, halved (hevc_core.h node_cost8_of);
+// node_cost4: the sum over its four 4x4 blocks of |DST-VII coefficients| (hevc_core.h dst4_row_stage,
+// node_cost4_of).  k_hevc_intra_modes: the same integers on the matrix cores.
+int node_cost8(const uint8_t* sy, int pitch, int x0, int y0, const int* pred, int bx, int by) {
+    int d[8][8];
+    for (int r = 0; r < 8; ++r)
+        for (int q = 0; q < 8; ++q)
+            d[r][q] = (int)sy[(size_t)(y0 + by + r) * pitch + x0 + bx + q] - pred[(by + r) * 16 + bx + q];
+    for (int pass = 0; pass < 2; ++pass)  // rows, then columns: 8-point Walsh-Hadamard
+        for (int r = 0; r < 8; ++r) {
+            int v[8];
+            for (int q = 0; q < 8; ++q) v[q] = pass ? d[q][r] : d[r][q];
+            for (int st = 1; st < 8; st <<= 1)
+                for (int i = 0; i < 8; i += 2 * st)
+                    for (int j = i; j < i + st; ++j) {
+                        const int a0 = v[j], a1 = v[j + st];
+                        v[j] = a0 + a1;
+                        v[j + st] = a0 - a1;
+                    }
+            for (int q = 0; q < 8; ++q) (pass ? d[q][r] : d[r][q]) = v[q];
+        }
+    int sum = 0;
+    for (int r = 0; r < 8; ++r)
+        for (int q = 0; q < 8; ++q) sum += std::abs(d[r][q]);
+    return node_cost8_of(sum);
+}
+int node_cost4(const uint8_t* sy, int pitch, int x0, int y0, const int* pred, int bx, int by) {
+    int sum = 0;
+    for (int j = 0; j < 4; ++j) {
+        const int tx = bx + (j & 1) * 4, ty = by + (j >> 1) * 4;
+        int t1[16];
+        for (int y = 0; y < 4; ++y)
+            for (int k = 0; k < 4; ++k) {
+                int a = 0;
+                for (int n = 0; n < 4; ++n)
+                    a += kDst4[k * 4 + n] * ((int)sy[(size_t)(y0 + ty + y) * pitch + x0 + tx + n] - pred[(ty + y) * 16 + tx + n]);
+                t1[y * 4 + k] = dst4_row_stage(a);
+            }
+        for (int k2 = 0; k2 < 4; ++k2)
+            for (int k = 0; k < 4; ++k) {
+                int a = 0;
+                for (int y = 0; y < 4; ++y) a += kDst4[k2 * 4 + y] * t1[y * 4 + k];
+                sum += std::abs(a);
+            }
+    }
+    return node_cost4_of(sum);
+}
+
 // Substituted references (intra_refs) of the N x N block at (x, y) of a plane -- step 1: luma, 2: one
 // NV12 chroma component (p at its first sample) -- with availability avl (split_tu_avl bits).
 void block_refs(const uint8_t* p, int pitch, int step, int x, int y, int N, int avl, int* L, int* T) {
@@ -456,9 +506,12 @@ void block_refs(const uint8_t* p, int pitch, int step, int x, int y, int N, int 
 // coarse-to-fine (intra_mode_search: at most 15 of the 35 modes); the lowest cost wins, ties to the
 // lower mode.  With split, the modes are searched again (same order) for the unit predicted as four
 // 8x8 TUs from the source (split_tu_avl; a CTB's first unit only in safe_split modes), and that mode
-// with kIntraSplitFlag wins when intra_split_wins over the unsplit cost (mode bits included).
+// with kIntraSplitFlag wins when intra_split_wins over the unsplit cost (mode bits included).  With tu4
+// (tree depth 2) the nodes of a unit whose split won are then compared, in that mode, as one 8x8 TU
+// against four 4x4 TUs predicted from the source around the node (split_tu4_avl without the node's own
+// TUs; intra_tu4_wins) -- *tu4: their mask.
 int intra_decide_mode(const uint8_t* sy, int pitch, int mb_w, int mb_h, int x, int y, int sr, int seg_w, int qp,
-                      uint64_t safe, uint64_t safe_split, bool split) {
+                      uint64_t safe, uint64_t safe_split, bool split, int* tu4) {
     const int x0 = x * 16, y0 = y * 16, z = ((y & 1) << 1) | (x & 1);
     int xb, xe;
     i_seg_range(x, seg_w, mb_w, xb, xe);
@@ -496,7 +549,31 @@ int intra_decide_mode(const uint8_t* sy, int pitch, int mb_w, int mb_h, int x, i
         return satd16(sy, pitch, x0, y0, pred) + lambda * intra_mode_bits(m, 1, 1);
     };
     const int best_s = intra_mode_search(cost_split);
-    return intra_split_wins(cost(best), cost_split(best_s), lambda) ? best_s | kIntraSplitFlag : best;
+    if (!intra_split_wins(cost(best), cost_split(best_s), lambda)) return best;
+    if (tu4) {
+        // per 8x8 node, in the split tree's mode: one 8x8 TU (pred holds the unit after cost_split)
+        // or four 4x4 TUs predicted from the source around the node, each costed in its own transform
+        // (intra_tu4_wins)
+        *tu4 = 0;
+        cost_split(best_s);
+        for (int k = 0; k < 4; ++k) {
+            const int bx = (k & 1) * 8, by = (k >> 1) * 8;
+            const int cost8 = node_cost8(sy, pitch, x0, y0, pred, bx, by);
+            if (!intra_tu4_possible(cost8, lambda)) continue;
+            if (k == 2 && bl_pending && !intra_tu4_bl_safe(best_s)) continue;
+            int p16[256];
+            for (int j = 0; j < 4; ++j) {
+                const int tx = bx + (j & 1) * 4, ty = by + (j >> 1) * 4;
+                int L4[9], T4[9], p4[16];
+                block_refs(sy, pitch, 1, x0 + tx, y0 + ty, 4, split_tu4_avl(k, j, al, ac, at, atr, false, false), L4, T4);
+                intra_predict(best_s, 2, 0, L4, T4, p4);
+                for (int r = 0; r < 4; ++r)
+                    for (int q = 0; q < 4; ++q) p16[(ty + r) * 16 + tx + q] = p4[r * 4 + q];
+            }
+            if (intra_tu4_wins(cost8, node_cost4(sy, pitch, x0, y0, p16, bx, by), lambda)) *tu4 |= 1 << k;
+        }
+    }
+    return best_s | kIntraSplitFlag;
 }
 
 void CpuHevcEncoder::analyse_intra(const uint8_t* sy, const uint8_t* suv, int pitch) {
@@ -518,8 +595,9 @@ void CpuHevcEncoder::analyse_intra(const uint8_t* sy, const uint8_t* suv, int pi
             int xb, xe;
             i_seg_range(x, common_.i_seg_w(), W, xb, xe);
             const bool al = x > xb, at = (y % sr) != 0, atr = at && x + 1 < xe && z != 3, ac = at && x > xb;
+            int tu4 = 0;
             const int dm = intra_decide_mode(sy, pitch, W, H, x, y, sr, common_.i_seg_w(), qp, bl_safe_, bl_safe_split_,
-                                             split_on);
+                                             split_on, common_.depth_intra() >= 2 ? &tu4 : nullptr);
             const int best = dm & (kIntraSplitFlag - 1);
             c.type = kCuIntra;
             c.intra_mode = (uint8_t)best;
@@ -530,18 +608,36 @@ void CpuHevcEncoder::analyse_intra(const uint8_t* sy, const uint8_t* suv, int pi
                 // four 8x8 luma TUs, then per TU its two 4x4 chroma TUs, each predicted from the
                 // reconstruction so far (ry / ruv hold it as the TUs complete)
                 c.tu_split = 2;
+                c.tu4 = (uint8_t)tu4;
                 const int scan = intra_scan_idx(best);
                 for (int k = 0; k < 4; ++k) {
                     const int avl = split_tu_avl(k, al, ac, at, atr);
                     const int bx = x0 + (k & 1) * 8, by = y0 + (k >> 1) * 8;
-                    int Lk[17], Tk[17], p8[64], r8[64], rr8[64];
-                    block_refs(ry, cw_, 1, bx, by, 8, avl, Lk, Tk);
-                    intra_predict(best, 3, 0, Lk, Tk, p8);
-                    for (int r = 0; r < 8; ++r)
-                        for (int q = 0; q < 8; ++q) r8[r * 8 + q] = sy[(size_t)(by + r) * pitch + bx + q] - p8[r * 8 + q];
-                    tu_encode(3, r8, qp, true, co + 64 * k, rr8, scan);
-                    for (int r = 0; r < 8; ++r)
-                        for (int q = 0; q < 8; ++q) ry[(by + r) * cw_ + bx + q] = (uint8_t)clip255(p8[r * 8 + q] + rr8[r * 8 + q]);
+                    if ((tu4 >> k) & 1) {
+                        // four 4x4 luma TUs in z order (DST-VII), each from the reconstruction so far
+                        for (int j = 0; j < 4; ++j) {
+                            const int tx = bx + (j & 1) * 4, ty = by + (j >> 1) * 4;
+                            int L4[9], T4[9], p4[16], r4[16], rr4[16];
+                            block_refs(ry, cw_, 1, tx, ty, 4, split_tu4_avl(k, j, al, ac, at, atr, false), L4, T4);
+                            intra_predict(best, 2, 0, L4, T4, p4);
+                            for (int r = 0; r < 4; ++r)
+                                for (int q = 0; q < 4; ++q) r4[r * 4 + q] = sy[(size_t)(ty + r) * pitch + tx + q] - p4[r * 4 + q];
+                            tu4_intra_encode(r4, qp, co + 64 * k + 16 * j, rr4, scan);
+                            for (int r = 0; r < 4; ++r)
+                                for (int q = 0; q < 4; ++q)
+                                    ry[(ty + r) * cw_ + tx + q] = (uint8_t)clip255(p4[r * 4 + q] + rr4[r * 4 + q]);
+                        }
+                    } else {
+                        int Lk[17], Tk[17], p8[64], r8[64], rr8[64];
+                        block_refs(ry, cw_, 1, bx, by, 8, avl, Lk, Tk);
+                        intra_predict(best, 3, 0, Lk, Tk, p8);
+                        for (int r = 0; r < 8; ++r)
+                            for (int q = 0; q < 8; ++q) r8[r * 8 + q] = sy[(size_t)(by + r) * pitch + bx + q] - p8[r * 8 + q];
+                        tu_encode(3, r8, qp, true, co + 64 * k, rr8, scan);
+                        for (int r = 0; r < 8; ++r)
+                            for (int q = 0; q < 8; ++q)
+                                ry[(by + r) * cw_ + bx + q] = (uint8_t)clip255(p8[r * 8 + q] + rr8[r * 8 + q]);
+                    }
                     const int cx = bx / 2, cy = by / 2;
                     for (int comp = 0; comp < 2; ++comp) {
                         int Lc[9], Tc[9], p4[16], r4[16], rr4[16];
@@ -892,8 +988,9 @@ namespace hevc {
 // Random slices (every CU type, CU32 and CU16 coding trees, split and unsplit transform trees,
 // levels up to the escape range, SAO parameters) coded twice -- directly and through the
 // bin-token path -- must give identical bytes.  Returns the number of slices checked; throws on
-// the first mismatch.
-int token_selftest(uint32_t seed, int slices) {
+// the first mismatch.  intra_tu4: intra units carry 4x4 luma nodes as well, under
+// max_transform_hierarchy_depth_intra 2 (the default draws the same slices as before).
+int token_selftest(uint32_t seed, int slices, bool intra_tu4) {
     uint32_t r = seed * 2654435761u + 1u;
     auto rnd = [&r](uint32_t n) {
         r ^= r << 13;
@@ -952,8 +1049,9 @@ int token_selftest(uint32_t seed, int slices) {
                     cu.mvdy = (int16_t)((int)rnd(64) - 32);
                     cu.mvp_idx = (uint8_t)(cu.type == kCuAmvp ? rnd(2) : rnd(5));
                 }
-                cu.tu_split = (uint8_t)(1 + rnd(2));  // intra too (max_transform_hierarchy_depth_intra 1 below)
-                cu.tu4 = (cu.tu_split == 2 && cu.type != kCuIntra) ? (uint8_t)rnd(16) : 0;  // 8x8 nodes into 4x4 TUs
+                cu.tu_split = (uint8_t)(1 + rnd(2));  // intra too (max_transform_hierarchy_depth_intra 1 or 2 below)
+                // 8x8 nodes into 4x4 TUs (intra units with intra_tu4 only)
+                cu.tu4 = (cu.tu_split == 2 && (intra_tu4 || cu.type != kCuIntra)) ? (uint8_t)rnd(16) : 0;
                 if (cu.type != kCuSkip) fill_levels(cu, i);
                 qpp[(size_t)i] = (uint8_t)(10 + rnd(40));
             }
@@ -968,7 +1066,7 @@ int token_selftest(uint32_t seed, int slices) {
         }
         const bool use_sao = rnd(2) != 0;
         const PicSyn ps{cus.data(), coef.data(), qpp.data(), use_sao ? sao.data() : nullptr, mb_w, mb_h,
-                        rnd(2) ? 3 : 0, 1};
+                        rnd(2) ? 3 : 0, intra_tu4 ? 2 : 1};
         const uint32_t cap = (uint32_t)(end - first) * 16384 + 1024;
         std::vector<uint8_t> a(cap), b(cap);
         std::vector<uint16_t> tok(kMaxCuTokens);

@@ -39,6 +39,7 @@ void GpuHevcEncoder::alloc_slot(FrameSlot& sl) {
     HIP_CHECK(hipMalloc(&b.qpy, ncu));
     HIP_CHECK(hipMalloc(&b.qp_pred, ncu));
     HIP_CHECK(hipMalloc(&b.imode, ncu));
+    HIP_CHECK(hipMalloc(&b.itu4, ncu));
     // arrays scanned in 4096-entry tiles of 16-byte loads (per CTB costs, per coding position token
     // counts): padded with zeros to a whole tile
     auto pad = [](size_t n) { return (n + kScanTilePad - 1) / kScanTilePad * kScanTilePad + 4; };
@@ -78,7 +79,7 @@ void GpuHevcEncoder::alloc_slot(FrameSlot& sl) {
 void GpuHevcEncoder::free_slot(FrameSlot& sl) {
     HevcDeviceBuffers& b = sl.buf;
     for (void* p : {(void*)b.fs, (void*)b.me.fs, (void*)b.me.mb, (void*)b.cu, (void*)b.coef, (void*)b.slice_data,
-                    (void*)b.slice_len, (void*)b.slice_first, (void*)b.slice_of_cu, (void*)b.nslices, (void*)b.qpy, (void*)b.qp_pred, (void*)b.imode, (void*)b.cost, (void*)b.qpc,
+                    (void*)b.slice_len, (void*)b.slice_first, (void*)b.slice_of_cu, (void*)b.nslices, (void*)b.qpy, (void*)b.qp_pred, (void*)b.imode, (void*)b.itu4, (void*)b.cost, (void*)b.qpc,
                     (void*)b.sse_part, (void*)b.sse_tot, (void*)b.sao, (void*)b.slice_clk, (void*)b.tok, (void*)b.ntok, (void*)b.tok_off,
                     (void*)b.tok_dense, (void*)b.wpp_ctx, (void*)b.wpp_flag, (void*)b.pack_done})
         if (p) (void)hipFree(p);
@@ -287,7 +288,8 @@ void GpuHevcEncoder::enqueue_analysis_impl(bool idr, const uint8_t* src_y, const
     if (idr) {
         if (cfg_.aq >= 3)  // the next P picture's temporal classes compare against this source
             launch_hevc_save_src(geom_, sl.buf, src_y, stream_);
-        launch_hevc_intra(geom_, sl.buf, 2 * common_.slice_rows(), common_.num_slices(), src_y, src_uv, stream_);
+        launch_hevc_intra(geom_, sl.buf, 2 * common_.slice_rows(), common_.num_slices(), common_.depth_intra(), src_y,
+                          src_uv, stream_);
     } else {
         h264::launch_hpel(geom_, sl.buf.me, hp_, hp_pitch_, stream_);
         h264::launch_me(geom_, sl.buf.me, src_y, stream_);

@@ -45,8 +45,8 @@ class HevcCommon {
     // quadrants at depth 1 may split too), else 0
     int depth_inter() const { return config().tu_split ? 3 : 0; }
     // max_transform_hierarchy_depth_intra: 1 when intra CU16s may split into four 8x8 luma / 4x4 chroma
-    // TUs (EncoderConfig::hevc_intra_split), else 0
-    int depth_intra() const { return config().hevc_intra_split ? 1 : 0; }
+    // TUs (EncoderConfig::hevc_intra_split), 2 when those 8x8 luma nodes may split again into 4x4 TUs, else 0
+    int depth_intra() const { return config().hevc_intra_split >= 2 ? 2 : (config().hevc_intra_split ? 1 : 0); }
     int slice_rows() const { return slice_rows_; }  // CTB rows per I slice
     int i_split() const { return i_split_; }        // I slices per CTB row (segments)
     int i_seg_w() const { return 2 * ((c32_w() + i_split_ - 1) / i_split_); }  // 16x16-unit columns per segment
@@ -85,11 +85,13 @@ class HevcCommon {
 };
 
 // Open-loop intra mode of a 16x16 unit (hevc_cpu.cpp; the GPU's k_hevc_intra_modes), with
-// kIntraSplitFlag set when split (nonzero safe_split) codes it as four 8x8 TUs.
+// kIntraSplitFlag set when split (nonzero safe_split) codes it as four 8x8 TUs.  With tu4 (tree
+// depth 2) it receives the mask of the split unit's 8x8 nodes that go on to four 4x4 luma TUs.
 int intra_decide_mode(const uint8_t* sy, int pitch, int mb_w, int mb_h, int x, int y, int sr, int seg_w, int qp,
-                      uint64_t safe, uint64_t safe_split = 0, bool split = false);
-// Direct vs bin-token CABAC on random slices (hevc_cpu.cpp); returns the slices checked.
-int token_selftest(uint32_t seed, int slices);
+                      uint64_t safe, uint64_t safe_split = 0, bool split = false, int* tu4 = nullptr);
+// Direct vs bin-token CABAC on random slices (hevc_cpu.cpp); returns the slices checked.  intra_tu4:
+// intra units get 4x4 luma nodes too, under max_transform_hierarchy_depth_intra 2.
+int token_selftest(uint32_t seed, int slices, bool intra_tu4 = false);
 // Entropy-code the slice of CTBs [first, end) with wavefront parallel processing (host): every CTB
 // row of the slice is a substream (fresh contexts in the slice's first row -- or when the picture
 // is one CTB wide -- else the contexts the row above had after its second CTB), written to `out` back to back;
@@ -193,7 +195,7 @@ struct HevcFrameState {
     int32_t depth_inter;  // max_transform_hierarchy_depth_inter of the SPS
     int32_t deblock_auto;  // EncoderConfig::deblock 2: k_hevc_db_auto decides deblock_on (h264_deblock.h rule)
     int32_t chroma_keep;   // EncoderConfig::hevc_chroma_keep: changing content keeps its chroma residual
-    int32_t depth_intra;   // max_transform_hierarchy_depth_intra of the SPS (1: intra units may split)
+    int32_t depth_intra;   // max_transform_hierarchy_depth_intra of the SPS (1: intra units may split, 2: 4x4 luma TUs)
 };
 
 struct HevcOutHeader {
@@ -233,6 +235,7 @@ struct HevcDeviceBuffers {
     uint8_t* qpy;            // [ncu] QpY per unit (deblocking)
     uint8_t* qp_pred;        // [ncu] QP predictor per unit (entropy coder)
     uint8_t* imode;          // [ncu] intra mode per unit (k_hevc_intra_modes, I pictures)
+    uint8_t* itu4;           // [ncu] 4x4 luma node mask of split intra units (k_hevc_intra_modes; CuInfo::tu4)
     uint32_t* cost;          // [nctb] CABAC cost estimate per CTB (slice layout)
     uint8_t* qpc;            // [ncu] QP of units that code a residual, else 255
     uint32_t* sao;           // [nctb][4] SAO parameters per CTB (hevc_core.h sao_pack; luma, Cb, Cr, 0)
@@ -260,7 +263,7 @@ void launch_hevc_publish(const HevcDeviceBuffers& b, const HevcFrameState& fs, c
 void launch_hevc_save_src(const Geometry& g, const HevcDeviceBuffers& b, const uint8_t* src_y, hipStream_t s);
 void launch_hevc_inter(const Geometry& g, const HevcDeviceBuffers& b, const uint8_t* src_y, const uint8_t* src_uv,
                        hipStream_t s);
-void launch_hevc_intra(const Geometry& g, const HevcDeviceBuffers& b, int slice_rows, int num_slices,
+void launch_hevc_intra(const Geometry& g, const HevcDeviceBuffers& b, int slice_rows, int num_slices, int depth_intra,
                        const uint8_t* src_y, const uint8_t* src_uv, hipStream_t s);
 // Slice layout, per-slice decisions and (with deblock) the in-loop filter + final distortion:
 // runs on the analysis stream because the deblocked picture is the next frame's reference.

@@ -67,10 +67,15 @@ struct alignas(16) Mats {
     int16_t tt16[256];  // transposed: tt16[y * 16 + k] = t16[k * 16 + y] (inverse stages)
     int16_t tt8[64];
     int16_t tt4[16];
+    int16_t dst4[16];   // DST-VII of 4x4 intra luma TUs (hevc_core.h kDst4) and its transpose
+    int16_t dstt4[16];
 };
 __device__ __forceinline__ void fill_mats(Mats& m) {
-    for (int i = threadIdx.x; i < 256 + 64 + 16; i += blockDim.x) {
-        if (i < 256) {
+    for (int i = threadIdx.x; i < 256 + 64 + 16 + 16; i += blockDim.x) {
+        if (i >= 336) {
+            m.dst4[i - 336] = kDst4[i - 336];
+            m.dstt4[i - 336] = kDst4[((i - 336) & 3) * 4 + ((i - 336) >> 2)];
+        } else if (i < 256) {
             m.t16[i] = (int16_t)dct_coef(4, i >> 4, i & 15);
             m.tt16[i] = (int16_t)dct_coef(4, i & 15, i >> 4);
         } else if (i < 320) {
@@ -1096,6 +1101,19 @@ __device__ __forceinline__ void split_refs_finish(SplitRefs& S, bool al, bool ac
     wave_lds_sync();
 }
 
+// Source references of the sixteen 4x4 luma TUs of a unit (index 4k + j: TU j of node k; from outside
+// node k only, substituted,
+// never smoothed at nTbS 4) and their DC values, for the 4x4-versus-8x8 choice of k_hevc_intra_modes.
+struct Tu4Refs {
+    int L[16][9], T[16][9];
+    int dc[16];
+};
+// position (x, y) relative to its block of reference p of ref_subst_idx's search order
+__device__ __forceinline__ void ref_pos(int p, int N, int* x, int* y) {
+    *x = p <= 2 * N ? -1 : p - 2 * N - 1;
+    *y = p < 2 * N ? 2 * N - 1 - p : -1;
+}
+
 // ------------------------------------------------------------------ intra mode decision (I)
 // Open-loop, every unit of an I picture at once (one wave per unit, a workgroup per CTB): the
 // modes predicted from the *source* neighbours with the decoder's z-order availability (never the
@@ -1103,13 +1121,20 @@ __device__ __forceinline__ void split_refs_finish(SplitRefs& S, bool al, bool ac
 // its below-left), scored by 4x4 Hadamard SATD + lambda * mode bits, searched coarse-to-fine
 // (intra_mode_search: at most 15 of the 35 modes) -- hevc_cpu.cpp
 // intra_decide_mode.  With intra splits on, the modes are searched again for four 8x8 TUs predicted
-// from the source (split_tu_avl), and kIntraSplitFlag is set with that mode when intra_split_wins.  The IDR wavefront
+// from the source (split_tu_avl), and kIntraSplitFlag is set with that mode when intra_split_wins.  With
+// tree depth 2 every 8x8 node of a unit whose split won is then costed in that mode as one 8x8 TU and as
+// four 4x4 TUs predicted from the source around the node (split_tu4_avl without the node's own TUs, no
+// smoothing), each in its own transform
+// (hevc_cpu.cpp node_cost8 / node_cost4): the same two products with diag(H8, H8) and with diag(DST-VII
+// x 4) in place of H16, the per-node sums taken from the lanes that hold the node (intra_tu4_wins; mask
+// to itu4).  The IDR wavefront
 // (k_hevc_intra) then only reconstructs.
 __global__ __launch_bounds__(256) void k_hevc_intra_modes(Geometry g, const HevcFrameState* __restrict__ fs,
                                                            const uint8_t* __restrict__ src_y,
-                                                           uint8_t* __restrict__ imode) {
+                                                           uint8_t* __restrict__ imode, uint8_t* __restrict__ itu4) {
     __shared__ IntraRefs rf[4];
     __shared__ SplitRefs srf[4];
+    __shared__ Tu4Refs trf[4];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int bid = blockIdx.x, cw = ctb_cols(g.mb_w);
     const int x = 2 * (bid % cw) + (wave & 1), y = 2 * (bid / cw) + (wave >> 1);
@@ -1192,7 +1217,7 @@ __global__ __launch_bounds__(256) void k_hevc_intra_modes(Geometry g, const Hevc
         return wave_sum(sad) + lambda * intra_mode_bits(m, 1, 1);
     };
     const int best = intra_mode_search(cost);  // coarse-to-fine: at most 15 of the 35 modes
-    int out = best;
+    int out = best, tu4 = 0;
     const int cost16 = cost(best);
     if (fs->depth_intra > 0 && intra_split_possible(cost16, lambda)) {  // the split tree's own mode search (wave-uniform)
         SplitRefs& S = srf[wave];
@@ -1231,9 +1256,207 @@ __global__ __launch_bounds__(256) void k_hevc_intra_modes(Geometry g, const Hevc
             return wave_sum(sad) + lambda * intra_mode_bits(m, 1, 1);
         };
         const int best_s = intra_mode_search(cost_split);
-        if (intra_split_wins(cost16, cost_split(best_s), lambda)) out = best_s | kIntraSplitFlag;
+        if (intra_split_wins(cost16, cost_split(best_s), lambda)) {
+            out = best_s | kIntraSplitFlag;
+            if (fs->depth_intra >= 2) {  // 4x4 luma TUs per 8x8 node (wave-uniform throughout)
+                // the accumulator lane holds rows 4 (l >> 4) .. + 3 of column l & 15: all in one node
+                const int node_s = ((lane >> 5) << 1) | ((lane >> 3) & 1);
+                // sum |M R M^T| per node, M block diagonal with this lane's entries mm[j] = M[l & 15][cb + j]
+                // (as hm): the B operand of the row product R M^T and the A operand of the column product.
+                // dst: the row product is rounded to the residual's scale first (dst4_row_stage; then
+                // |values| <= 482 are exact in f16 -- the Hadamard's are integers up to 2040)
+                auto node_sums = [&](const mf_h4 a, const mf_h4 mm, bool dst, int* n) {
+                    const mf_f4 t = __builtin_amdgcn_mfma_f32_16x16x16f16(a, mm, zero, 0, 0, 0);
+                    mf_h4 tb;
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) tb[i] = (_Float16)(dst ? dst4_row_stage((int)t[i]) : (int)t[i]);
+                    const mf_f4 sm = __builtin_amdgcn_mfma_f32_16x16x16f16(mm, tb, zero, 0, 0, 0);
+                    const int sad = (int)(__builtin_fabsf(sm[0]) + __builtin_fabsf(sm[1]) + __builtin_fabsf(sm[2]) +
+                                          __builtin_fabsf(sm[3]));
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) n[k] = wave_sum(node_s == k ? sad : 0);
+                };
+                mf_h4 h8m, dm;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int row = lane & 15, k = cb + j;
+                    h8m[j] = (_Float16)((row >> 3) == (k >> 3) ? (__popc((row & 7) & (k & 7)) & 1 ? -1 : 1) : 0);
+                    dm[j] = (_Float16)((row >> 2) == (k >> 2) ? (int)kDst4[(row & 3) * 4 + (k & 3)] : 0);
+                }
+                int n8[4], n4[4];
+                mf_h4 a;
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    a[j] = (_Float16)((int)((sw >> (8 * j)) & 0xff) -
+                                      pred_sample(best_s, 3, true, S.L[kq], S.T[kq], S.LF[kq], S.TF[kq], S.dc[kq],
+                                                  (cb + j) & 7, r & 7));
+                node_sums(a, h8m, false, n8);
+                int cand = 0;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) n8[k] = node_cost8_of(n8[k]);
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    if (intra_tu4_possible(n8[k], lambda) && !(k == 2 && bl_pending && !intra_tu4_bl_safe(best_s)))
+                        cand |= 1 << k;
+                if (cand) {
+                    Tu4Refs& Q = trf[wave];
+                    for (int i = lane; i < 16 * 17; i += 64) {  // references of the sixteen TUs, from the source
+                        const int tu = i / 17, q = i - tu * 17, k = tu >> 2, j = tu & 3;
+                        const int tx = (k & 1) * 8 + (j & 1) * 4, ty = (k >> 1) * 8 + (j >> 1) * 4;
+                        const int p = ref_subst_idx(q, 4, split_tu4_avl(k, j, al, ac, at, atr, false, false));
+                        int v = 128;
+                        if (p >= 0) {
+                            int xx, yy;
+                            ref_pos(p, 4, &xx, &yy);
+                            v = src_y[(size_t)(y0 + ty + yy) * P + x0 + tx + xx];
+                        }
+                        if (q < 8) Q.L[tu][8 - q] = v;
+                        else if (q == 8) Q.L[tu][0] = Q.T[tu][0] = v;
+                        else Q.T[tu][q - 8] = v;
+                    }
+                    wave_lds_sync();
+                    if (lane < 16) {
+                        int sum = 4;
+                        for (int q = 1; q <= 4; ++q) sum += Q.L[lane][q] + Q.T[lane][q];
+                        Q.dc[lane] = sum >> 3;
+                    }
+                    wave_lds_sync();
+                    // the lane's four samples (row r, columns cb .. cb + 3) are one row of TU (cb >> 2, r >> 2)
+                    const int gx = cb >> 2, gy = r >> 2;
+                    const int tu = ((gy >> 1) << 3) | ((gx >> 1) << 2) | ((gy & 1) << 1) | (gx & 1);
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+                        a[j] = (_Float16)((int)((sw >> (8 * j)) & 0xff) -
+                                          pred_sample(best_s, 2, true, Q.L[tu], Q.T[tu], Q.L[tu], Q.T[tu], Q.dc[tu], j, r & 3));
+                    node_sums(a, dm, true, n4);
+#pragma unroll
+                    for (int k = 0; k < 4; ++k)
+                        if (((cand >> k) & 1) && intra_tu4_wins(n8[k], node_cost4_of(n4[k]), lambda)) tu4 |= 1 << k;
+                }
+            }
+        }
     }
-    if (lane == 0) imode[y * g.mb_w + x] = (uint8_t)out;
+    if (lane == 0) {
+        imode[y * g.mb_w + x] = (uint8_t)out;
+        itu4[y * g.mb_w + x] = (uint8_t)tu4;
+    }
+}
+
+// Chroma reference q (ref_subst_idx's search order, N = 4) of component c of TU k of a split intra
+// unit: from the unit's neighbours (R) or the reconstruction of the TUs before it (t.pred).
+__device__ __forceinline__ int split_chroma_ref(const IntraRefs& R, const TuBuf& t, int c, int q, int k, int avl) {
+    const int cbx = (k & 1) * 4, cby = (k >> 1) * 4;
+    const int j = ref_subst_idx(q, 4, avl);
+    const uint8_t* up = t.pred + 256 + c * 64;
+    if (j < 0) return 128;
+    if (j < 8) {
+        const int r = 7 - j;
+        return r < 4 ? (cbx == 0 ? R.lc[c][cby + r] : up[(cby + r) * 8 + cbx - 1]) : R.lc[c][r];
+    }
+    if (j == 8) return k == 0 ? R.corner_c[c] : (k == 1 ? R.tc[c][3] : (k == 2 ? R.lc[c][3] : up[3 * 8 + 3]));
+    if (j <= 12) {
+        const int d = j - 9;
+        return cby == 0 ? R.tc[c][cbx + d] : up[3 * 8 + cbx + d];
+    }
+    const int d = j - 13;
+    return k == 0 ? R.tc[c][4 + d] : (k == 1 ? R.trc[c][d] : up[3 * 8 + 4 + d]);
+}
+// Reconstructed luma sample (ux, uy) relative to the unit's origin: the unit's own reconstruction so
+// far (t.pred) or its left / corner / top / top-right neighbours (ux >= -1, uy in [-1, 16), ux < 32
+// above the unit, ux < 16 inside it).
+__device__ __forceinline__ int unit_rec_y(const IntraRefs& R, const TuBuf& t, int ux, int uy) {
+    if (uy < 0) return ux < 0 ? R.corner : (ux < 16 ? R.tpx[ux] : R.trx[ux - 16]);
+    return ux < 0 ? R.lpx[uy] : t.pred[uy * 16 + ux];
+}
+
+// Node k of a split intra unit as four 4x4 luma TUs (CuInfo::tu4), in z order: a TU is one 16-lane
+// row, one sample per lane (x = lane & 3, y = (lane >> 2) & 3).  Its 17 references come straight from R
+// and t.pred (no smoothing at nTbS 4) into S, one hand-off; prediction, the forward DST-VII,
+// quantisation, dequantisation and the inverse run in registers, the two 4-point stages of each
+// direction through shuffles inside the row (quad, then stride 4); the second hand-off publishes the
+// reconstruction in t.pred for the next TU.  The node's two 4x4 chroma TUs (core transform) do not
+// depend on its luma and ride along with the first luma TU in rows 1 (Cb) and 2 (Cr).  Same integers
+// as tu4_intra_encode / tu_encode_t<2> of the CPU encoder.  sse: per-lane partial sums (Y, Cb, Cr).
+__device__ __forceinline__ void split_intra_node4(TuBuf& t, SplitRefs& S, const IntraRefs& R, const Mats& M,
+                                                  const uint8_t* src, int16_t* lv, int mode, int scan, int qp, int qpc,
+                                                  int k, bool al, bool ac, bool at, bool atr, int16_t* coef,
+                                                  uint8_t* rec_y, uint8_t* rec_uv, int pitch, int x0, int y0, int disp_w,
+                                                  int disp_h, int* sse) {
+    const int lane = threadIdx.x & 63;
+    const int grp = lane >> 4, a = lane & 3, b = (lane >> 2) & 3, qb = lane & ~3, gb = lane & ~15;
+    const int gs = grp < 3 ? grp : 0;  // row 3 idles (computes row 0's values, stores nothing)
+    const int bx = (k & 1) * 8, by = (k >> 1) * 8, cbx = bx >> 1, cby = by >> 1;
+    const int avl8 = split_tu_avl(k, al, ac, at, atr);
+    const int16_t* mt = grp == 0 ? M.dst4 : M.t4;     // [frequency][sample]
+    const int16_t* mtt = grp == 0 ? M.dstt4 : M.tt4;  // [sample][frequency]
+    const int q = grp == 0 ? qp : qpc;
+    const int si = scan_index_s(2, scan, a, b);
+#pragma unroll 1
+    for (int j = 0; j < 4; ++j) {
+        const int tx = bx + (j & 1) * 4, ty = by + (j >> 1) * 4;
+        if (lane < 17) {
+            const int p = ref_subst_idx(lane, 4, split_tu4_avl(k, j, al, ac, at, atr, false));
+            int v = 128;
+            if (p >= 0) {
+                int xx, yy;
+                ref_pos(p, 4, &xx, &yy);
+                v = unit_rec_y(R, t, tx + xx, ty + yy);
+            }
+            if (lane < 8) S.L[0][8 - lane] = v;
+            else if (lane == 8) S.L[0][0] = S.T[0][0] = v;
+            else S.T[0][lane - 8] = v;
+        } else if (j == 0 && lane < 17 + 34) {
+            const int c = (lane - 17) / 17, qq = (lane - 17) - c * 17;
+            const int v = split_chroma_ref(R, t, c, qq, k, avl8);
+            if (qq < 8) S.L[1 + c][8 - qq] = v;
+            else if (qq == 8) S.L[1 + c][0] = S.T[1 + c][0] = v;
+            else S.T[1 + c][qq - 8] = v;
+        }
+        wave_lds_sync();
+        const bool on = grp == 0 || (j == 0 && grp < 3);
+        const int* L = S.L[gs];
+        const int* T = S.T[gs];
+        const int q16 = lane & 15;
+        const int dc = (gsum<16>(q16 < 4 ? L[1 + q16] : (q16 < 8 ? T[q16 - 3] : 0)) + 4) >> 3;
+        const int pr = pred_sample(mode, 2, grp == 0, L, T, L, T, dc, a, b);
+        const int o = grp == 0 ? (ty + b) * 16 + tx + a : 256 + (gs - 1) * 64 + (cby + b) * 8 + cbx + a;
+        const int sv = src[o];
+        int v = sv - pr, acc = 0;
+#pragma unroll
+        for (int n = 0; n < 4; ++n) acc += mt[a * 4 + n] * __shfl(v, qb | n, 64);  // rows: (y = b, frequency a)
+        v = (acc + 1) >> 1;
+        acc = 0;
+#pragma unroll
+        for (int n = 0; n < 4; ++n) acc += mt[b * 4 + n] * __shfl(v, gb | (n << 2) | a, 64);  // columns: (b, a)
+        const int l = quant_coef((acc + 128) >> 8, q, 2, true);
+        if (on) {
+            const int ci = grp == 0 ? 64 * k + 16 * j + si : 256 + 64 * (grp - 1) + 16 * k + si;
+            coef[ci] = (int16_t)l;
+            lv[ci] = (int16_t)l;
+        }
+        v = dequant_coef(l, q, 2);
+        acc = 0;
+#pragma unroll
+        for (int n = 0; n < 4; ++n) acc += mtt[b * 4 + n] * __shfl(v, gb | (n << 2) | a, 64);  // inverse columns
+        v = clip16((acc + 64) >> 7);
+        acc = 0;
+#pragma unroll
+        for (int n = 0; n < 4; ++n) acc += mtt[a * 4 + n] * __shfl(v, qb | n, 64);  // inverse rows
+        const int rv = clip255(pr + ((acc + 2048) >> 12));
+        if (on) {
+            const int e = sv - rv;
+            t.pred[o] = (uint8_t)rv;
+            if (grp == 0) {
+                sse[0] += (x0 + tx + a < disp_w && y0 + ty + b < disp_h) ? e * e : 0;
+                rec_y[(size_t)(y0 + ty + b) * pitch + x0 + tx + a] = (uint8_t)rv;
+            } else {
+                const int xc = x0 / 2 + cbx + a, yc = y0 / 2 + cby + b;
+                sse[grp] += (2 * xc < disp_w && 2 * yc < disp_h) ? e * e : 0;
+                rec_uv[(size_t)yc * pitch + 2 * xc + grp - 1] = (uint8_t)rv;
+            }
+        }
+        wave_lds_sync();
+    }
 }
 
 // A split intra unit (kIntraSplitFlag) in the IDR wavefront, by its wave alone (wave-local LDS
@@ -1243,13 +1466,15 @@ __global__ __launch_bounds__(256) void k_hevc_intra_modes(Geometry g, const Hevc
 // unit's mode, then forward transform, quantisation (intra: no decimation, no trim), levels in the
 // mode's scan order, inverse transform and reconstruction into t.pred / rec -- as tu_encode_t<3> /
 // <2> of the CPU encoder's analyse_intra.  src: the unit's source (t.pred layout); lv: LDS copy of
-// the unit's levels (CU layout); the raw references go through S.
+// the unit's levels (CU layout); the raw references go through S.  tu4: the nodes coded as four 4x4
+// luma TUs (split_intra_node4).
 struct SplitIntraResult {
     int sse[3];
     uint32_t bits;  // cu_bits_est of the split tree
 };
+template <bool kTu4>
 __device__ SplitIntraResult split_intra_code(TuBuf& t, SplitRefs& S, const IntraRefs& R, const Mats& M,
-                                             const uint8_t* src, int16_t* lv, int mode, int qp, int qpc, bool al,
+                                             const uint8_t* src, int16_t* lv, int mode, int tu4, int qp, int qpc, bool al,
                                              bool ac, bool at, bool atr, int16_t* coef, uint8_t* rec_y,
                                              uint8_t* rec_uv, int pitch, int x0, int y0, int disp_w, int disp_h) {
     const int lane = threadIdx.x & 63;
@@ -1260,8 +1485,14 @@ __device__ SplitIntraResult split_intra_code(TuBuf& t, SplitRefs& S, const Intra
     int16_t* aT = reinterpret_cast<int16_t*>(t.a);  // stage buffers: luma [0, 64), chroma 64 + 16 comp
     int16_t* bT = reinterpret_cast<int16_t*>(t.b);
     int sse_y = 0, sse_c = 0;
+    int sse4[3] = {0, 0, 0};  // the 4x4 nodes' partial sums
 #pragma unroll 1
     for (int k = 0; k < 4; ++k) {
+        if (kTu4 && ((tu4 >> k) & 1)) {  // (wave-uniform)
+            split_intra_node4(t, S, R, M, src, lv, mode, scan, qp, qpc, k, al, ac, at, atr, coef, rec_y, rec_uv, pitch, x0,
+                              y0, disp_w, disp_h, sse4);
+            continue;
+        }
         const int bx = (k & 1) * 8, by = (k >> 1) * 8, cbx = bx >> 1, cby = by >> 1;
         const int avl = split_tu_avl(k, al, ac, at, atr);
         // ---- references in one pass: lane i < 33 takes luma reference i (ref_subst's search order:
@@ -1292,22 +1523,7 @@ __device__ SplitIntraResult split_intra_code(TuBuf& t, SplitRefs& S, const Intra
                 }
             } else if (i < 33 + 34) {
                 const int c = (i - 33) / 17, q = (i - 33) - c * 17;
-                const int j = ref_subst_idx(q, 4, avl);
-                const uint8_t* up = t.pred + 256 + c * 64;
-                if (j < 0) {
-                    v = 128;
-                } else if (j < 8) {
-                    const int r = 7 - j;
-                    v = r < 4 ? (cbx == 0 ? R.lc[c][cby + r] : up[(cby + r) * 8 + cbx - 1]) : R.lc[c][r];
-                } else if (j == 8) {
-                    v = k == 0 ? R.corner_c[c] : (k == 1 ? R.tc[c][3] : (k == 2 ? R.lc[c][3] : up[3 * 8 + 3]));
-                } else if (j <= 12) {
-                    const int d = j - 9;
-                    v = cby == 0 ? R.tc[c][cbx + d] : up[3 * 8 + cbx + d];
-                } else {
-                    const int d = j - 13;
-                    v = k == 0 ? R.tc[c][4 + d] : (k == 1 ? R.trc[c][d] : up[3 * 8 + 4 + d]);
-                }
+                v = split_chroma_ref(R, t, c, q, k, avl);
                 if (q < 8) S.L[1 + c][8 - q] = v;
                 else if (q == 8) S.L[1 + c][0] = S.T[1 + c][0] = v;
                 else S.T[1 + c][q - 8] = v;
@@ -1393,19 +1609,20 @@ __device__ SplitIntraResult split_intra_code(TuBuf& t, SplitRefs& S, const Intra
         wave_lds_sync();
     }
     SplitIntraResult out;
-    out.sse[0] = wave_sum(sse_y);
-    out.sse[1] = wave_sum(comp == 0 && cl ? sse_c : 0);
-    out.sse[2] = wave_sum(comp == 1 && cl ? sse_c : 0);
-    // cu_bits_est (split, no 4x4 luma): per TU 4 + 2 floor(log2 |l|) per level, + 4 if coded, else 1
+    out.sse[0] = wave_sum(sse_y + sse4[0]);
+    out.sse[1] = wave_sum((comp == 0 && cl ? sse_c : 0) + sse4[1]);
+    out.sse[2] = wave_sum((comp == 1 && cl ? sse_c : 0) + sse4[2]);
+    // cu_bits_est (split): per TU 4 + 2 floor(log2 |l|) per level, + 4 if coded, else 1; a 4x4 node's
+    // 64 levels are four TUs of 16, as a chroma component's
     uint32_t bits = 0;
 #pragma unroll
     for (int j = 0; j < 6; ++j) {
         const int l = lv[64 * j + lane], a = l < 0 ? -l : l;
         const int b = a ? 4 + 2 * (31 - __builtin_clz((uint32_t)a)) : 0;
-        if (j < 4) {
+        if (j < 4 && !(kTu4 && ((tu4 >> j) & 1))) {
             const int sum = wave_sum(b);
             bits += (uint32_t)(__ballot(a != 0) ? sum + 4 : 1);
-        } else {  // four 4x4 chroma TUs of 16 levels
+        } else {  // four 4x4 TUs of 16 levels
             const int sum = gsum<16>(b);
             const uint64_t any = __ballot(a != 0);
 #pragma unroll
@@ -1417,10 +1634,14 @@ __device__ SplitIntraResult split_intra_code(TuBuf& t, SplitRefs& S, const Intra
     return out;
 }
 
+// kTu4: tree depth 2 (hevc_intra_split 2) -- split units read their 4x4 node mask (itu4); the instance
+// without it holds no 4x4 code, so depths 0 and 1 keep the registers and the time they had
+template <bool kTu4>
 __global__ __launch_bounds__(64 * kMaxSliceRows) void k_hevc_intra(Geometry g, const HevcFrameState* __restrict__ fs,
                                                       const uint8_t* __restrict__ src_y,
                                                       const uint8_t* __restrict__ src_uv, CuInfo* __restrict__ cus,
                                                       int16_t* __restrict__ coef, const uint8_t* __restrict__ imode,
+                                                      const uint8_t* __restrict__ itu4,
                                                       uint8_t* __restrict__ qp_coded) {
     // a serial chain on few waves: issue priority over the bulk kernels sharing its SIMDs
     __builtin_amdgcn_s_setprio(3);
@@ -1515,13 +1736,14 @@ __global__ __launch_bounds__(64 * kMaxSliceRows) void k_hevc_intra(Geometry g, c
             }
             wave_lds_sync();
             int16_t* lvs = reinterpret_cast<int16_t*>(t.b) + 384;
+            const int tu4 = kTu4 ? uni((int)itu4[i]) : 0;  // 4x4 luma nodes (wave-uniform)
             const SplitIntraResult sres =
-                split_intra_code(t, srf[wave], R, M, sb, lvs, mode, qp, qpc, al, ac, at, atr, coef + (size_t)i * kCoefPerCu,
-                                 fs->rec_y, fs->rec_uv, g.pitch, x0, y0, g.width, g.height);
+                split_intra_code<kTu4>(t, srf[wave], R, M, sb, lvs, mode, tu4, qp, qpc, al, ac, at, atr,
+                                       coef + (size_t)i * kCoefPerCu, fs->rec_y, fs->rec_uv, g.pitch, x0, y0, g.width, g.height);
             acc[0] += (unsigned)sres.sse[0];
             acc[1] += (unsigned)sres.sse[1];
             acc[2] += (unsigned)sres.sse[2];
-            const SplitSummary ss = split_summary_wave(lvs, lane, 0);
+            const SplitSummary ss = split_summary_wave(lvs, lane, tu4);
             if (lane == 0) {
                 CuInfo c{};
                 c.type = kCuIntra;
@@ -2755,13 +2977,17 @@ void launch_hevc_inter(const Geometry& g, const HevcDeviceBuffers& b, const uint
                        b.qpc);
 }
 
-void launch_hevc_intra(const Geometry& g, const HevcDeviceBuffers& b, int slice_rows, int num_slices,
+void launch_hevc_intra(const Geometry& g, const HevcDeviceBuffers& b, int slice_rows, int num_slices, int depth_intra,
                        const uint8_t* src_y, const uint8_t* src_uv, hipStream_t s) {
     const int nctb = ctb_cols(g.mb_w) * ctb_rows(g.mb_h);
-    hipLaunchKernelGGL(k_hevc_intra_modes, dim3(nctb), dim3(256), 0, s, g, b.fs, src_y, b.imode);
+    hipLaunchKernelGGL(k_hevc_intra_modes, dim3(nctb), dim3(256), 0, s, g, b.fs, src_y, b.imode, b.itu4);
     const size_t lds = (size_t)slice_rows * 2 * g.coded_w;
-    hipLaunchKernelGGL(k_hevc_intra, dim3(num_slices), dim3(64 * slice_rows), lds, s, g, b.fs, src_y, src_uv, b.cu,
-                       b.coef, b.imode, b.qpc);
+    if (depth_intra >= 2)
+        hipLaunchKernelGGL(k_hevc_intra<true>, dim3(num_slices), dim3(64 * slice_rows), lds, s, g, b.fs, src_y, src_uv,
+                           b.cu, b.coef, b.imode, b.itu4, b.qpc);
+    else
+        hipLaunchKernelGGL(k_hevc_intra<false>, dim3(num_slices), dim3(64 * slice_rows), lds, s, g, b.fs, src_y, src_uv,
+                           b.cu, b.coef, b.imode, b.itu4, b.qpc);
 }
 
 void launch_hevc_layout(const Geometry& g, const HevcDeviceBuffers& b, bool idr, int max_slices, int slice_cost, bool deblock,

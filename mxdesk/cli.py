@@ -60,6 +60,7 @@ def build_pipeline(cfg: C.Config, device: int = 0, session_name: str = "0", capt
     return StreamPipeline(cfg.sizew, cfg.sizeh, cfg.stream_fps, backend=backend, device=device,
                           bitrate_kbps=cfg.video_bitrate, keyint=cfg.keyint_frames, search_range=cfg.search_range,
                           scroll_range=cfg.scroll_range, partitions=cfg.h264_partitions,
+                          hevc_intra_split=cfg.hevc_intra_split,
                           subpel=cfg.subpel, noise=cfg.noise, out_width=cfg.out_width, out_height=cfg.out_height,
                           session_name=session_name, capture=capture, codec=cfg.codec)
 

@@ -207,6 +207,8 @@ def apply_encoder_args(enc, a: dict) -> None:
     enc.scroll_range = a["scroll_range"]
     enc.partitions = a["partitions"]  # H.264 (HEVC and VP8 code 16x16 units whatever it says)
     enc.subpel = 1 if a["subpel"] else 0
+    if "hevc_intra_split" in a:  # HEVC I pictures: transform-tree depth (EncoderConfig::hevc_intra_split)
+        enc.hevc_intra_split = a["hevc_intra_split"]
 
 
 class StreamPipeline:
@@ -215,7 +217,8 @@ class StreamPipeline:
                  noise: bool = True, out_width: int = 0, out_height: int = 0, session_name: str = "0",
                  capture: Any = None, metrics: SessionMetrics | None = None, queue_frames: int | None = None,
                  stall_s: float = 2.0, paced: bool = True, codec: str = "h264",
-                 idr_min_interval_s: float | None = None, scroll_range: int = 0, partitions: int = 1):
+                 idr_min_interval_s: float | None = None, scroll_range: int = 0, partitions: int = 1,
+                 hevc_intra_split: int = 1):
         if codec not in CODEC_IDS:
             raise ValueError(f"unknown codec {codec!r} (h264 | hevc | vp8)")
         self.codec = codec
@@ -234,7 +237,8 @@ class StreamPipeline:
         self.paced = paced
         self.bitrate_kbps = bitrate_kbps  # configured CBR target (congestion control upper bound)
         self._enc_args = dict(bitrate_kbps=bitrate_kbps, keyint=keyint, search_range=search_range, subpel=subpel,
-                              noise=noise, scroll_range=scroll_range, partitions=partitions)
+                              noise=noise, scroll_range=scroll_range, partitions=partitions,
+                              hevc_intra_split=hevc_intra_split)
         self.last_scroll = (0, 0)  # scroll hint of the last P picture (H.264 with scroll_range; /status)
         self._subs: list[_Subscriber] = []
         self._lock = threading.Lock()

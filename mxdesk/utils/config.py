@@ -155,6 +155,9 @@ SCHEMA: list[Var] = [
         "H.264: largest scroll (luma samples, <= 192) the P-picture probe pass looks for; 0 = off"),
     Var("h264_partitions", ["MXDESK_H264_PARTITIONS"], 1, int,
         "H.264 P macroblock shapes: 0 = 16x16 only, 1 = and 16x8 / 8x16, 2 = and P_8x8 (a vector per 8x8 quadrant)"),
+    Var("hevc_intra_split", ["MXDESK_HEVC_INTRA_SPLIT"], 1, int,
+        "HEVC I pictures, transform tree of a 16x16 unit: 0 = one 16x16 luma TU, 1 = may split into four 8x8 luma TUs, "
+        "2 = and those into four 4x4 luma TUs (DST-VII)"),
     Var("subpel", ["MXDESK_SUBPEL"], True, bool, "quarter-pel motion refinement"),
     Var("noise", ["MXDESK_NOISE"], True, bool, "synthetic desktop: animated-noise panel"),
     Var("wall", ["MXDESK_WALL"], "", str, "tiled wall layout, e.g. '2x2' (one tile per GPU)"),
@@ -267,6 +270,8 @@ class Config:
             raise ValueError("MXDESK_SCROLL_RANGE must be in [0, 192]")
         if v["h264_partitions"] not in (0, 1, 2):
             raise ValueError("MXDESK_H264_PARTITIONS must be 0, 1 or 2")
+        if v["hevc_intra_split"] not in (0, 1, 2):
+            raise ValueError("MXDESK_HEVC_INTRA_SPLIT must be 0, 1 or 2")
         if v["source"] not in ("auto", "synthetic", "x11"):
             raise ValueError("MXDESK_SOURCE must be auto, synthetic or x11")
         self.encoder_backend  # noqa: B018  (raises on unknown encoders)
