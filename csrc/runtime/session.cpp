@@ -230,7 +230,7 @@ Session::~Session() {
         if (staging_[k]) (void)hipHostFree(staging_[k]);
     if (lt_mem_) hipFree(lt_mem_);
     if (lt_mf_mem_) hipFree(lt_mf_mem_);
-    for (const auto& r : host_regs_) (void)hipHostUnregister(const_cast<uint8_t*>(r.first));
+    for (void* p : host_locked_) (void)hipHostUnregister(p);
     if (screen_) (void)hipFree(screen_);
     if (ev_upload_) (void)hipEventDestroy(ev_upload_);
     if (upload_stream_) {
@@ -430,7 +430,29 @@ void Session::register_host_buffer(const void* p, size_t bytes) {
     const uint8_t* b = static_cast<const uint8_t*>(p);
     for (const auto& r : host_regs_)
         if (r.first == b && r.second == bytes) return;
-    HIP_CHECK(hipHostRegister(const_cast<void*>(p), bytes, hipHostRegisterDefault));
+    if (p == nullptr || bytes == 0) throw std::invalid_argument("register_host_buffer: empty range");
+    // a range HIP page-locked at allocation (hipHostMalloc, a pinned torch tensor) is DMA-able
+    // as it is, and registering it again is an error
+    auto pinned = [](const void* q) {
+        hipPointerAttribute_t a{};
+        if (hipPointerGetAttributes(&a, q) != hipSuccess) {
+            (void)hipGetLastError();  // an unknown pointer is no error of ours
+            return false;
+        }
+        return a.type == hipMemoryTypeHost;
+    };
+    if (!(pinned(b) && pinned(b + bytes - 1))) {
+        const hipError_t e = hipHostRegister(const_cast<void*>(p), bytes, hipHostRegisterDefault);
+        // a refusal (some virtual machines cannot page-lock existing memory) must not stay behind
+        // as the thread's last error: the caller goes on with the copy paths, whose launches
+        // check hipGetLastError()
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            throw std::runtime_error(std::string("HIP error ") + hipGetErrorString(e) +
+                                     " in register_host_buffer: hipHostRegister");
+        }
+        host_locked_.push_back(const_cast<void*>(p));
+    }
     host_regs_.emplace_back(b, bytes);
     ensure_upload_stream();
 }

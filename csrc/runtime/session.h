@@ -128,7 +128,9 @@ class Session {
     void submit_bgrx(const uint8_t* host_bgrx, int host_pitch, bool force_idr = false);
     // Page-locks a host buffer the capture writes frames into (e.g. the XShm segment):
     // submit_bgrx from inside it is a direct 2D DMA, with no copy into the staging buffer, and
-    // returns once the DMA has read the frame (the buffer may then be overwritten).
+    // returns once the DMA has read the frame (the buffer may then be overwritten).  A buffer
+    // HIP already page-locked (hipHostMalloc, pinned torch memory) is taken as it is.  Throws
+    // std::runtime_error where page-locking is refused; the copy paths stay usable.
     void register_host_buffer(const void* p, size_t bytes);
     // submit_bgrx from a raw host address whose readable extent is `bytes`: throws
     // std::invalid_argument unless the frame span (pitch * (height - 1) + width * 4) fits.
@@ -199,6 +201,7 @@ class Session {
     void* lt_mem_ = nullptr;
     void* lt_mf_mem_ = nullptr;  // MFMA scaler fragment tables
     std::vector<std::pair<const uint8_t*, size_t>> host_regs_;  // register_host_buffer ranges
+    std::vector<void*> host_locked_;  // those of them this session page-locked (to unregister)
     hipEvent_t ev_upload_ = nullptr;
     hipStream_t upload_stream_ = nullptr;  // zero-copy DMA from registered capture buffers
     uint8_t* screen_ = nullptr;  // device-resident screen (submit_bgrx_damage), pool pitch

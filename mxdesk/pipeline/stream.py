@@ -345,13 +345,16 @@ class StreamPipeline:
                 if shm is not None and (getattr(self.capture, "w", self.width), getattr(self.capture, "h", self.height)) \
                         != (self.width, self.height):
                     shm = None  # capture resized but the session not yet: copy path (size-checked)
-                if shm is not None and getattr(self, "_shm_reg", None) != shm:
+                asked = (getattr(self, "_shm_reg", None), getattr(self, "_shm_refused", None))
+                if shm is not None and shm not in asked:
                     try:
                         s.register_host_buffer(*shm)
                         self._shm_reg = shm
-                    except RuntimeError as e:  # page-locking refused: keep the staging copy path
+                    except RuntimeError as e:
+                        # page-locking refused (asked once per segment): whole frames keep the
+                        # staging copy path; damage bands are read from the pageable segment
                         log.warning("register_host_buffer failed (%s); using the staging copy", e)
-                        shm = None
+                        self._shm_refused = shm
                         self.capture_zero_copy = False
                 dmg = getattr(self.capture, "damage", None) if shm is not None else None
                 if dmg is not None:

@@ -17,6 +17,12 @@ def _stream():
     return torch.cuda.current_stream().cuda_stream
 
 
+def _pinned_rows(h, pitch):
+    """A zeroed (h, pitch) uint8 host array in memory page-locked at allocation: a stand-in for
+    a capture segment that also serves where existing memory cannot be page-locked."""
+    return torch.zeros((h, pitch), dtype=torch.uint8).pin_memory().numpy()
+
+
 def test_csc_matches_float_reference(gpu):
     rng = np.random.default_rng(0)
     h, w = 68, 120
@@ -464,7 +470,7 @@ def test_zero_copy_registered_capture_matches_staged_upload(gpu):
         return gpu.Session(cfg)
 
     staged, zc = session(), session()
-    buf = np.zeros((h, pitch), np.uint8)  # the "capture segment", registered once
+    buf = _pinned_rows(h, pitch)  # the "capture segment", registered once
     zc.register_host_buffer(buf.ctypes.data, buf.nbytes)
     for f in frames:
         staged.submit_bgrx(np.ascontiguousarray(f[:, : w * 4]).reshape(h, w, 4), False)
@@ -504,7 +510,7 @@ def test_damage_driven_capture_matches_full_upload(gpu, registered):
         return gpu.Session(cfg)
 
     full, dmg = session(), session()
-    buf = np.zeros((h, pitch), np.uint8)
+    buf = _pinned_rows(h, pitch) if registered else np.zeros((h, pitch), np.uint8)
     if registered:
         dmg.register_host_buffer(buf.ctypes.data, buf.nbytes)
     for i, (f, bands) in enumerate(seq):
