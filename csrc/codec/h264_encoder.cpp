@@ -260,6 +260,8 @@ void mc_luma_for_test(const uint8_t* ref, int coded_w, int coded_h, int pitch, i
 // ------------------------------------------------------------------ GpuH264Encoder
 // Events that only order GPU work between this device's queues: a device-scope release when
 // recorded (the default system-scope release writes the caches back for the host each time).
+// (the release scope applies where the event is recorded; as a kernel's stop event -- analysis_done on
+// k_p_fused -- the runtime's launch path picks it)
 constexpr unsigned kDeviceEvent = hipEventDisableTiming | hipEventReleaseToDevice;
 
 void GpuH264Encoder::alloc_slot(FrameSlot& sl) {
@@ -422,9 +424,10 @@ void GpuH264Encoder::launcher_loop() {
         try {
             FrameSlot& sl = slots_[j.slot];
             HIP_CHECK(hipStreamWaitEvent(j.stream, sl.analysis_done, 0));
-            launch_entropy(geom_, sl.buf, sl.host_out, j.stream, j.sse_ready, sl.scroll.hint, cfg_.partitions >= 2);
+            // sl.done is k_pack's stop event: the last kernel of the in-order entropy stream
+            launch_entropy(geom_, sl.buf, sl.host_out, j.stream, j.sse_ready, sl.scroll.hint, cfg_.partitions >= 2,
+                           sl.done);
             HIP_CHECK(hipGetLastError());
-            HIP_CHECK(hipEventRecord(sl.done, j.stream));
         } catch (...) {
             std::lock_guard<std::mutex> lk(lmu_);
             lerr_ = std::current_exception();
@@ -484,8 +487,10 @@ GpuH264Encoder::~GpuH264Encoder() {
     for (int i = 0; i < depth_; ++i) free_slot(slots_[i]);
 }
 
-void GpuH264Encoder::enqueue_analysis_kernels(bool idr, const uint8_t* src_y, const uint8_t* src_uv, bool publish) {
+bool GpuH264Encoder::enqueue_analysis_kernels(bool idr, const uint8_t* src_y, const uint8_t* src_uv, bool publish,
+                                              hipEvent_t done) {
     FrameSlot& sl = slots_[prep_slot_];
+    bool carried = false;  // `done` went with the picture's last analysis kernel
     const FrameState* pub = publish ? sl.fs_host : nullptr;
     auto wait_input = [&]() {
         if (!in_ev_) return;
@@ -522,7 +527,9 @@ void GpuH264Encoder::enqueue_analysis_kernels(bool idr, const uint8_t* src_y, co
             // the search reads the picture the coder predicts from: one kernel searches and codes
             wait_input();
             if (scroll) launch_scroll_probe(geom_, sl.buf, *scroll, src_y, stream_, pub);
-            launch_p_fused(geom_, sl.buf, src_y, src_uv, stream_, pub, scroll, quads);
+            // k_p_fused is the picture's last analysis kernel unless the intra pass follows
+            carried = done && !cfg_.intra_in_p;
+            launch_p_fused(geom_, sl.buf, src_y, src_uv, stream_, pub, scroll, quads, carried ? done : nullptr);
         } else {
             wait_input();
             if (scroll) launch_scroll_probe(geom_, sl.buf, *scroll, src_y, stream_, pub);
@@ -531,6 +538,7 @@ void GpuH264Encoder::enqueue_analysis_kernels(bool idr, const uint8_t* src_y, co
         }
         if (cfg_.intra_in_p) launch_intra_in_p(geom_, sl.buf, src_y, src_uv, stream_);
     }
+    return carried;
 }
 
 void GpuH264Encoder::link_entropy() {
@@ -556,10 +564,12 @@ void GpuH264Encoder::unfiltered_copy(FrameSlot& sl) {
 
 void GpuH264Encoder::enqueue_kernels(bool idr, const uint8_t* src_y, const uint8_t* src_uv, bool publish) {
     FrameSlot& sl = slots_[prep_slot_];
-    enqueue_analysis_kernels(idr, src_y, src_uv, publish);
     async_frame_ = launcher_.joinable() && publish && !sync_launch_;
+    // eager frames whose entropy chain waits for analysis_done alone: the event goes with the last
+    // analysis kernel where there is one such kernel (k_p_fused), else it is recorded behind them
+    const bool carried = enqueue_analysis_kernels(idr, src_y, src_uv, publish, async_frame_ ? sl.analysis_done : nullptr);
     if (async_frame_) {  // entropy chain to the launcher thread (its stream operations only there)
-        HIP_CHECK(hipEventRecord(sl.analysis_done, stream_));
+        if (!carried) HIP_CHECK(hipEventRecord(sl.analysis_done, stream_));
         hipEvent_t sse_ready = nullptr;
         if (sl.deblock) {
             unfiltered_copy(sl);
@@ -699,7 +709,7 @@ void GpuH264Encoder::record_start() {}
 void GpuH264Encoder::record_done() {
     FrameSlot& sl = slots_[prep_slot_];
     if (async_frame_) {
-        async_frame_ = false;  // the launcher records sl.done after the entropy kernels
+        async_frame_ = false;  // sl.done goes with the launcher's k_pack (its stop event)
     } else {
         slot_job_[prep_slot_] = 0;
         HIP_CHECK(hipEventRecord(sl.done, stream_e_ ? stream_e_ : stream_));

@@ -287,7 +287,7 @@ class GpuH264Encoder final : public VideoEncoder {
     void link_entropy() override;
     void quiesce() override { drain_launcher(); }
     // The wait goes directly before the picture's first kernel: on the queue it then follows the
-    // previous picture's analysis_done record without a kernel between the two barrier packets
+    // previous picture's last analysis kernel (or its analysis_done record) with no kernel between
     bool set_input_event(hipEvent_t ev) override {
         in_ev_ = ev;
         return true;
@@ -304,7 +304,10 @@ class GpuH264Encoder final : public VideoEncoder {
     // publish: the first kernel takes the frame state by value and stores it (eager launches);
     // otherwise the kernels read the device copy uploaded by enqueue_body's memcpy node.
     void enqueue_kernels(bool idr, const uint8_t* src_y, const uint8_t* src_uv, bool publish);
-    void enqueue_analysis_kernels(bool idr, const uint8_t* src_y, const uint8_t* src_uv, bool publish);
+    // done: an event to complete with the picture's analysis.  Returns true if its last kernel
+    // carries it (launch_with_event); false leaves the hipEventRecord to the caller.
+    bool enqueue_analysis_kernels(bool idr, const uint8_t* src_y, const uint8_t* src_uv, bool publish,
+                                  hipEvent_t done = nullptr);
 
    private:
     struct FrameSlot {  // per-frame-in-flight state
@@ -337,7 +340,7 @@ class GpuH264Encoder final : public VideoEncoder {
         hipStream_t stream;  // the entropy stream of this picture
     };
     void launcher_loop();
-    void wait_launched(int slot) const;  // the job that records slots_[slot].done was issued
+    void wait_launched(int slot) const;  // the job whose k_pack carries slots_[slot].done was issued
     void drain_launcher() const;         // every queued job issued
     std::thread launcher_;
     mutable std::mutex lmu_;

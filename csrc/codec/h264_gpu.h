@@ -229,7 +229,8 @@ void launch_inter(const Geometry& g, const DeviceBuffers& b, const uint8_t* src_
                   hipStream_t stream, bool quads = false);
 // launch_me + launch_inter as one kernel (k_p_fused): a workgroup per macroblock searches, then codes
 // it on one wave.  For a P picture whose search reads the picture the coder predicts from
-// (FrameState::me_ref null); `publish` as launch_me.  The encoder uses it up to kFusedMaxMbs
+// (FrameState::me_ref null); `publish` as launch_me; `done`: if set, the kernel's stop event
+// (launch_with_event).  The encoder uses it up to kFusedMaxMbs
 // macroblocks (1080p), where the search leaves compute units idle in its tail and the coding fills
 // them (+1.7 %); at 2560x1440 and 4K the search fills the GPU, and running it at the fused kernel's
 // 6 waves per SIMD instead of k_me_full's 8 costs more than the overlap returns (-4 %, -8 %:
@@ -237,7 +238,7 @@ void launch_inter(const Geometry& g, const DeviceBuffers& b, const uint8_t* src_
 constexpr int kFusedMaxMbs = 8160;
 void launch_p_fused(const Geometry& g, const DeviceBuffers& b, const uint8_t* src_y, const uint8_t* src_uv,
                     hipStream_t stream, const FrameState* publish = nullptr, const ScrollBuffers* scroll = nullptr,
-                    bool quads = false);
+                    bool quads = false, hipEvent_t done = nullptr);
 // The first kernel of a frame (launch_intra for I, launch_me / launch_p_fused for P) publishes the frame
 // state: with `publish` non-null it takes the state by value and stores it to b.fs for the
 // later kernels (no copy node); with nullptr it reads b.fs (filled by a memcpy node, hipGraph).
@@ -262,8 +263,10 @@ void launch_save_src(const Geometry& g, const DeviceBuffers& b, const uint8_t* s
 // reduced (the deblocking kernels' completion on the analysis stream), or nullptr
 // scroll_hint: the P picture's hint (ScrollBuffers::hint) for OutHeader::scroll_dx / dy, or nullptr
 // quads: the picture may hold P_8x8 macroblocks (launch_me): k_cavlc<true> writes their sub_mb_pred syntax
+// done: if set, k_pack's stop event (launch_with_event): it completes with the chain's last kernel
 void launch_entropy(const Geometry& g, const DeviceBuffers& b, uint8_t* host_out, hipStream_t stream,
-                    hipEvent_t wait_for_sse = nullptr, const int32_t* scroll_hint = nullptr, bool quads = false);
+                    hipEvent_t wait_for_sse = nullptr, const int32_t* scroll_hint = nullptr, bool quads = false,
+                    hipEvent_t done = nullptr);
 // P pictures, after launch_inter: open-loop intra analysis of every MB (intra vs inter) and the
 // closed-loop reconstruction of the MBs that switched to intra.
 void launch_intra_in_p(const Geometry& g, const DeviceBuffers& b, const uint8_t* src_y, const uint8_t* src_uv,

@@ -32,6 +32,7 @@
 #include <cstddef>
 
 #include "../common/hip_check.h"
+#include "../common/launch_event.h"
 #include "../common/wave.h"
 #include "h264_core.h"
 #include "h264_deblock.h"
@@ -3197,15 +3198,16 @@ void launch_inter(const Geometry& g, const DeviceBuffers& b, const uint8_t* src_
 }
 
 void launch_p_fused(const Geometry& g, const DeviceBuffers& b, const uint8_t* src_y, const uint8_t* src_uv,
-                    hipStream_t stream, const FrameState* publish, const ScrollBuffers* scroll, bool quads) {
+                    hipStream_t stream, const FrameState* publish, const ScrollBuffers* scroll, bool quads,
+                    hipEvent_t done) {
     const int nmb = g.mb_w * g.mb_h;
     const StateArg sa = make_state_arg(b, publish, !scroll);
     if (scroll)
-        hipLaunchKernelGGL(quads ? k_p_fused_scroll_q8 : k_p_fused_scroll, dim3(nmb), dim3(kMeThreads), 0, stream, g, sa, src_y, src_uv, b.mb, b.coef,
-                           b.mb_sse, b.wave_prog, scroll->hint);
+        launch_with_event(done, quads ? k_p_fused_scroll_q8 : k_p_fused_scroll, dim3(nmb), dim3(kMeThreads), stream, g, sa, src_y, src_uv, b.mb, b.coef,
+                          b.mb_sse, b.wave_prog, scroll->hint);
     else
-        hipLaunchKernelGGL(quads ? k_p_fused_q8 : k_p_fused, dim3(nmb), dim3(kMeThreads), 0, stream, g, sa, src_y, src_uv, b.mb, b.coef,
-                           b.mb_sse, b.wave_prog);
+        launch_with_event(done, quads ? k_p_fused_q8 : k_p_fused, dim3(nmb), dim3(kMeThreads), stream, g, sa, src_y, src_uv, b.mb, b.coef,
+                          b.mb_sse, b.wave_prog);
 }
 
 static void launch_analyze(const Geometry& g, const DeviceBuffers& b, const uint8_t* src_y, const uint8_t* src_uv,
@@ -3252,7 +3254,7 @@ void launch_save_src(const Geometry& g, const DeviceBuffers& b, const uint8_t* s
 }
 
 void launch_entropy(const Geometry& g, const DeviceBuffers& b, uint8_t* host_out, hipStream_t stream,
-                    hipEvent_t wait_for_sse, const int32_t* scroll_hint, bool quads) {
+                    hipEvent_t wait_for_sse, const int32_t* scroll_hint, bool quads, hipEvent_t done) {
     const int nmb = g.mb_w * g.mb_h;
     hipLaunchKernelGGL(quads ? k_cavlc<true> : k_cavlc<false>, dim3((nmb + kCavlcMbPerBlock - 1) / kCavlcMbPerBlock), dim3(256), 0, stream, g, b.fs,
                        b.mb, b.coef, b.slot,
@@ -3264,8 +3266,8 @@ void launch_entropy(const Geometry& g, const DeviceBuffers& b, uint8_t* host_out
                        b.row_sse, b.mb, b.db_cnt, b.mb_sse);
     hipLaunchKernelGGL(k_scan_out, dim3(g.mb_h), dim3(kScanThreads), 0, stream, g, b.fs, b.slot_bits, b.row_agg,
                        b.row_sse, b.coded_info, b.slice_info, b.out_bytes, b.out_hdr, b.quad_unit, b.db_cnt, scroll_hint);
-    hipLaunchKernelGGL(k_pack, dim3(256), dim3(256), 0, stream, g, b.fs, b.slot, b.coded_info, b.slice_info,
-                       b.out_hdr, host_out, b.quad_unit, b.pack_done);
+    launch_with_event(done, k_pack, dim3(256), dim3(256), stream, g, b.fs, b.slot, b.coded_info, b.slice_info,
+                      b.out_hdr, host_out, b.quad_unit, b.pack_done);
 }
 
 }  // namespace h264

@@ -48,8 +48,10 @@ void launch_synth_dev(uint8_t* bgrx, const SynthParams* d_params, int width, int
 // BGRx -> NV12 (BT.709 limited range), padding the output to (coded_w, coded_h) by edge
 // replication.  Output Y plane pitch = UV plane pitch = out_pitch.
 // ts: if set, the device wall clock at the kernel's start is stored there (frame GPU time).
+// done: if set, an event that completes with the kernel (its stop event, common/launch_event.h).
 void launch_bgrx_to_nv12(const uint8_t* bgrx, int in_pitch, int w, int h, uint8_t* y, uint8_t* uv, int out_pitch,
-                         int coded_w, int coded_h, hipStream_t stream, uint64_t* ts = nullptr);
+                         int coded_w, int coded_h, hipStream_t stream, uint64_t* ts = nullptr,
+                         hipEvent_t done = nullptr);
 
 // Fused separable Lanczos-3 resample (in_w x in_h -> out_w x out_h) + BT.709 CSC into
 // NV12, LDS-tiled.  `weights` from make_lanczos_tables (device memory).

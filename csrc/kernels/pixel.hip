@@ -20,6 +20,7 @@
 
 #include "pixel.h"
 #include "../common/hip_check.h"
+#include "../common/launch_event.h"
 
 namespace mx {
 namespace pix {
@@ -1292,11 +1293,11 @@ void launch_synth_dev(uint8_t* bgrx, const SynthParams* d_params, int width, int
 }
 
 void launch_bgrx_to_nv12(const uint8_t* bgrx, int in_pitch, int w, int h, uint8_t* y, uint8_t* uv, int out_pitch,
-                         int coded_w, int coded_h, hipStream_t stream, uint64_t* ts) {
+                         int coded_w, int coded_h, hipStream_t stream, uint64_t* ts, hipEvent_t done) {
     dim3 block(64, 4);
     dim3 grid((coded_w / 4 + 63) / 64, (coded_h / 2 + 3) / 4);
-    hipLaunchKernelGGL(k_bgrx_to_nv12, grid, block, 0, stream, bgrx, in_pitch, w, h, y, uv, out_pitch, coded_w,
-                       coded_h, ts);
+    launch_with_event(done, k_bgrx_to_nv12, grid, block, stream, bgrx, in_pitch, w, h, y, uv, out_pitch, coded_w,
+                      coded_h, ts);
 }
 
 bool build_scale_frags(int in_w, int in_h, int out_w, int out_h, int coded_w, int coded_h,

@@ -128,7 +128,9 @@ Session::Session(const SessionConfig& cfg) : cfg_(cfg) {
         } else {
             HIP_CHECK(hipStreamCreateWithFlags(&cap_stream_, hipStreamNonBlocking));
         }
-        for (int k = 0; k < depth_; ++k)  // GPU-to-GPU only: device-scope release
+        // GPU-to-GPU only: device-scope release where the event is recorded (scaler path); as the stop
+        // event of k_bgrx_to_nv12 the runtime's launch path picks the release scope (not measured apart)
+        for (int k = 0; k < depth_; ++k)
             HIP_CHECK(hipEventCreateWithFlags(&ev_conv_[k], hipEventDisableTiming | hipEventReleaseToDevice));
     }
     if (depth_ > 1 && cfg_.use_graph && !enc_->supports_split())
@@ -246,7 +248,7 @@ Session::~Session() {
     hipStreamDestroy(stream_);
 }
 
-void Session::convert(int slot, hipStream_t st, uint64_t* ts) {
+bool Session::convert(int slot, hipStream_t st, uint64_t* ts, hipEvent_t done) {
     const h264::Geometry& g = enc_->geometry();
     uint8_t* y = nv12_y_[cur_k_];
     uint8_t* uv = nv12_uv_[cur_k_];
@@ -255,9 +257,10 @@ void Session::convert(int slot, hipStream_t st, uint64_t* ts) {
                                   g.coded_w, g.coded_h, st, ts);
     } else {
         pix::launch_bgrx_to_nv12(pool_->data(slot), pool_->pitch(), cfg_.width, cfg_.height, y, uv, g.pitch,
-                                 g.coded_w, g.coded_h, st, ts);
+                                 g.coded_w, g.coded_h, st, ts, done);
     }
     HIP_CHECK(hipGetLastError());
+    return done && !scale_;
 }
 
 void Session::convert_and_encode(int slot, bool force_idr, bool stamp) {
@@ -398,9 +401,9 @@ void Session::submit_synthetic(bool force_idr) {
         pix::launch_synth(pool_->data(slot), p, cs, synth_bg_);
         HIP_CHECK(hipGetLastError());
         TraceRange tr2("mxdesk.convert+encode.enqueue");
-        convert(slot, cs);
+        const bool carried = convert(slot, cs, nullptr, cap_stream_ ? ev_conv_[k] : nullptr);
         if (cap_stream_) {
-            HIP_CHECK(hipEventRecord(ev_conv_[k], cs));
+            if (!carried) HIP_CHECK(hipEventRecord(ev_conv_[k], cs));
             // the encoder waits right before its first source read (or here, if it cannot)
             if (!enc_->set_input_event(ev_conv_[k])) HIP_CHECK(hipStreamWaitEvent(stream_, ev_conv_[k], 0));
         }

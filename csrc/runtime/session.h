@@ -173,7 +173,9 @@ class Session {
     bool capture_stream_active() const { return cap_stream_ != nullptr; }
 
    private:
-    void convert(int slot, hipStream_t st, uint64_t* ts = nullptr);
+    // done: an event to complete with the conversion.  Returns true if the kernel carries it (the
+    // unscaled conversion); false leaves the hipEventRecord to the caller.
+    bool convert(int slot, hipStream_t st, uint64_t* ts = nullptr, hipEvent_t done = nullptr);
     // stamp: the conversion stores the frame's start clock (capture paths; the synthetic path's
     // render stamps it)
     void convert_and_encode(int slot, bool force_idr, bool stamp);
