@@ -2270,16 +2270,14 @@ constexpr uint32_t kLambdaSse16[52] = {1,    1,    1,    1,    1,    2,     2,  
                                        14825, 18678, 23533, 29649, 37356, 47065, 59298, 74711};
 // Rough CABAC bits of one TU's levels: ~3.5 bins per significant level plus the magnitude
 // (Golomb-Rice growth), ~4 bits of last position / cbf overhead per coded TU.
+MXHD int level_bits(int l) {  // the term of one level (0 for a zero)
+    const int a = l < 0 ? -l : l;
+    return a ? 4 + 2 * (31 - __builtin_clz((uint32_t)a)) : 0;
+}
 MXHD uint32_t tu_bits_est(const int16_t* lv, int n) {
     uint32_t b = 0;
-    bool any = false;
-    for (int k = 0; k < n; ++k) {
-        const int a = lv[k] < 0 ? -lv[k] : lv[k];
-        if (!a) continue;
-        any = true;
-        b += 4 + 2 * (31 - __builtin_clz((uint32_t)a));
-    }
-    return any ? b + 4 : 1;
+    for (int k = 0; k < n; ++k) b += (uint32_t)level_bits(lv[k]);
+    return b ? b + 4 : 1;
 }
 // Split wins when its SSE + lambda * bits is lower (costs in 1/16 units).
 // The split tree is tried only for CUs whose unsplit tree coded at least one level: a residual

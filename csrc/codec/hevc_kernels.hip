@@ -6,7 +6,8 @@
 //                  compensation, the 16x16 / 8x8 core transforms as LDS-staged
 //                  matrix products (4 luma + 2 chroma outputs per lane per stage),
 //                  quantisation, normative inverse transform and reconstruction, coded
-//                  sub-block / last-position summaries by wave reductions.
+//                  sub-block / last-position summaries by wave reductions.  The TU stages
+//                  themselves (every size, decimation, trailing trim) are in hevc_tu.h.
 //  * k_hevc_intra  one workgroup per slice, one wave per unit row; the rows of a slice run
 //                  as a wavefront (a unit waits until the row above finished the units
 //                  above and above-right: per-row progress counters in LDS, no workgroup
@@ -35,90 +36,17 @@
 #include "h264_mb.h"
 #include "hevc_core.h"
 #include "hevc_encoder.h"
+#include "hevc_tu.h"
 
 namespace mx {
 namespace hevc {
 
 namespace {
 
-// reductions inside aligned groups of G lanes (G = 8 or 16): every lane gets its group's value
-template <int G>
-__device__ __forceinline__ int gsum(int v) {
-    for (int o = G / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-template <int G>
-__device__ __forceinline__ int gmax(int v) {
-    for (int o = G / 2; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
-    return v;
-}
-// Stage separator of the TU helpers: wave-local (every wave has its own LDS scratch; the intra
-// wavefront's rows synchronise through progress counters, not workgroup barriers).
-template <bool kWaveLocal>
-__device__ __forceinline__ void tu_sync() {
-    wave_lds_sync();  // both users run their waves alone (the intra wavefront through progress counters)
-}
-
-// Transform matrices in LDS (filled once per workgroup).
-struct alignas(16) Mats {
-    int16_t t16[256];
-    int16_t t8[64];
-    int16_t t4[16];
-    int16_t tt16[256];  // transposed: tt16[y * 16 + k] = t16[k * 16 + y] (inverse stages)
-    int16_t tt8[64];
-    int16_t tt4[16];
-    int16_t dst4[16];   // DST-VII of 4x4 intra luma TUs (hevc_core.h kDst4) and its transpose
-    int16_t dstt4[16];
-};
-__device__ __forceinline__ void fill_mats(Mats& m) {
-    for (int i = threadIdx.x; i < 256 + 64 + 16 + 16; i += blockDim.x) {
-        if (i >= 336) {
-            m.dst4[i - 336] = kDst4[i - 336];
-            m.dstt4[i - 336] = kDst4[((i - 336) & 3) * 4 + ((i - 336) >> 2)];
-        } else if (i < 256) {
-            m.t16[i] = (int16_t)dct_coef(4, i >> 4, i & 15);
-            m.tt16[i] = (int16_t)dct_coef(4, i & 15, i >> 4);
-        } else if (i < 320) {
-            m.t8[i - 256] = (int16_t)dct_coef(3, (i - 256) >> 3, (i - 256) & 7);
-            m.tt8[i - 256] = (int16_t)dct_coef(3, (i - 256) & 7, (i - 256) >> 3);
-        } else {
-            m.t4[i - 320] = (int16_t)dct_coef(2, (i - 320) >> 2, (i - 320) & 3);
-            m.tt4[i - 320] = (int16_t)dct_coef(2, (i - 320) & 3, (i - 320) >> 2);
-        }
-    }
-}
-
-// Integer dot products of 16 / 8 int16 pairs from 16-byte aligned LDS rows with v_dot2 (two
-// multiply-adds per VALU instruction, one ds_read_b128 per 8 values).  Exact: int32 sums.
-typedef short mx_short2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ int dot2acc(uint32_t a, uint32_t b, int c) {
-    return __builtin_amdgcn_sdot2(__builtin_bit_cast(mx_short2, a), __builtin_bit_cast(mx_short2, b), c, false);
-}
-__device__ __forceinline__ int dot8(const int16_t* a, const int16_t* b) {
-    const uint4 x = *reinterpret_cast<const uint4*>(a), y = *reinterpret_cast<const uint4*>(b);
-    return dot2acc(x.w, y.w, dot2acc(x.z, y.z, dot2acc(x.y, y.y, dot2acc(x.x, y.x, 0))));
-}
-__device__ __forceinline__ int dot4(const int16_t* a, const int16_t* b) {  // 8-byte aligned rows
-    const uint2 x = *reinterpret_cast<const uint2*>(a), y = *reinterpret_cast<const uint2*>(b);
-    return dot2acc(x.y, y.y, dot2acc(x.x, y.x, 0));
-}
-__device__ __forceinline__ int dot16(const int16_t* a, const int16_t* b) { return dot8(a, b) + dot8(a + 8, b + 8); }
-
-// Per-wave TU scratch: residual / prediction / two int32 stage buffers for 256 luma +
-// 2 x 64 chroma samples (code_tus keeps int16 stage values in them, laid out so that every
-// transform stage reads contiguous 16-byte rows: see its comments).
-struct alignas(16) TuBuf {
-    int16_t res[384];
-    uint8_t pred[384];
-    int32_t a[384];
-    int32_t b[384];
-};
-
-// One wave transforms, quantises and reconstructs its CU's three TUs.  Lane mapping per
-// stage: luma outputs lane*4 .. lane*4+3, chroma outputs (lane&31)*2 .. +1 of component
-// lane>>5.  tu_sync<kInterCu>() (wave-local) separates the stages; intra CUs (kInterCu false)
-// keep their reconstruction in t.pred for the neighbours, inter CUs leave t.pred (the prediction)
-// intact for the split tree after it.
+// One wave transforms, quantises and reconstructs its CU's three TUs: the 16x16 luma TU on the
+// whole wave (4 outputs per lane), the two 8x8 chroma TUs on its two halves (component lane >> 5,
+// 2 outputs per lane).  Intra CUs (kInterCu false) keep their reconstruction in t.pred for the
+// neighbours, inter CUs leave t.pred (the prediction) intact for the split tree after it.
 struct TuResult {
     int last[3];
     uint32_t csbf[3];
@@ -131,138 +59,45 @@ struct TuResult {
 };
 
 template <bool kInterCu>
-__device__ __forceinline__ TuResult code_tus(TuBuf& t, const Mats& M, int qp, int qpc, bool intra, bool valid,
-                                             int16_t* coef, uint8_t* rec_y, int pitch_y, uint8_t* rec_uv, int x0,
-                                             int y0, int disp_w, int disp_h) {
-    const int lane = threadIdx.x & 63;
-    const int comp = lane >> 5, cl = lane & 31;
-    // int16 views of the stage buffers: aT = forward stage 1 transposed (aT[k][y]), bT = the
-    // dequantised levels transposed (bT[x][k]), a16 = inverse stage 1 (a16[y][x]); forward
-    // stage 1 fits 16 bits (|res| <= 255, row sums of |T| <= 1024 before the >> 3 / >> 2)
-    int16_t* aT = reinterpret_cast<int16_t*>(t.a);
-    int16_t* a16 = reinterpret_cast<int16_t*>(t.a);
-    int16_t* bT = reinterpret_cast<int16_t*>(t.b);
-    // ---- forward stage 1 (rows): a[y][k] = sum_n T[k][n] res[y][n]
+__device__ __forceinline__ TuResult code_tus(TuBuf& t, const Mats& M, int qp, int qpc, bool valid, int16_t* coef,
+                                             uint8_t* rec_y, int pitch_y, uint8_t* rec_uv, int x0, int y0,
+                                             int disp_w, int disp_h) {
+    constexpr bool intra = !kInterCu;
+    const int lane = threadIdx.x & 63, comp = lane >> 5;
+    const TuAt ul = {0, 16, 0}, uc = {256 + comp * 64, 8, 256 + comp * 64};
     if (valid) {
-        for (int j = 0; j < 4; ++j) {
-            const int idx = lane * 4 + j, y = idx >> 4, k = idx & 15;
-            const int s = dot16(M.t16 + k * 16, t.res + y * 16);
-            aT[k * 16 + y] = (int16_t)((s + 4) >> 3);
-        }
-        for (int j = 0; j < 2; ++j) {
-            const int idx = cl * 2 + j, y = idx >> 3, k = idx & 7;
-            const int16_t* r = t.res + 256 + comp * 64;
-            const int s = dot8(M.t8 + k * 8, r + y * 8);
-            aT[256 + comp * 64 + k * 8 + y] = (int16_t)((s + 2) >> 2);
-        }
+        tu_fwd_rows<4, 4>(t, M, ul);
+        tu_fwd_rows<3, 2>(t, M, uc);
     }
-    tu_sync<kInterCu>();
+    wave_lds_sync();
+    int ll[4] = {0, 0, 0, 0}, lc[2] = {0, 0}, sil[4] = {0, 0, 0, 0}, sic[2] = {0, 0};
+    if (valid) {
+        tu_fwd_cols_quant<4, 4>(t, M, ul, qp, intra, ll, sil);
+        tu_fwd_cols_quant<3, 2>(t, M, uc, qpc, intra, lc, sic);
+    }
+    tu_decimate_group<64>(ll, 4, intra);
+    tu_decimate_group<32>(lc, 3, intra);
+    if (!intra) {
+        tu_trim_group<64>(ll, sil);
+        tu_trim_group<32>(lc, sic);
+    }
     TuResult out;
     int lastl = -1, lastc = -1, nzl = 0, nzc = 0;
-    uint32_t csl = 0, csc = 0;
-    // ---- forward stage 2 (columns) + quantisation (levels kept in registers)
-    int ll[4] = {0, 0, 0, 0}, lc[2] = {0, 0};
-    int mxl = 0, mxc = 0;
-    if (valid) {
-        for (int j = 0; j < 4; ++j) {
-            const int idx = lane * 4 + j, k2 = idx >> 4, k = idx & 15;
-            const int s = dot16(M.t16 + k2 * 16, aT + k * 16);
-            ll[j] = quant_coef((s + 512) >> 10, qp, 4, intra);
-            nzl += ll[j] != 0;
-            mxl = max(mxl, abs(ll[j]));
-        }
-        for (int j = 0; j < 2; ++j) {
-            const int idx = cl * 2 + j, k2 = idx >> 3, k = idx & 7;
-            const int s = dot8(M.t8 + k2 * 8, aT + 256 + comp * 64 + k * 8);
-            lc[j] = quant_coef((s + 256) >> 9, qpc, 3, intra);
-            nzc += lc[j] != 0;
-            mxc = max(mxc, abs(lc[j]));
-        }
-    }
-    // decimation (wave-uniform decisions per TU), then levels / dequantised values / summaries
-    const bool drop_y = tu_decimate(4, intra, wave_sum(nzl), wave_max(mxl));
-    const bool drop_cb = tu_decimate(3, intra, wave_sum(comp == 0 ? nzc : 0), wave_max(comp == 0 ? mxc : 0));
-    const bool drop_cr = tu_decimate(3, intra, wave_sum(comp == 1 ? nzc : 0), wave_max(comp == 1 ? mxc : 0));
-    const bool drop_c = comp ? drop_cr : drop_cb;
-    if (drop_y)
-        for (int j = 0; j < 4; ++j) ll[j] = 0;
-    if (drop_c)
-        for (int j = 0; j < 2; ++j) lc[j] = 0;
-    if (!intra) {
-        // trailing isolated +-1 trim (tu_encode rule), one TU after the other; the lane owning
-        // the last level clears it
-        for (int it = 0; it < kTrimIters; ++it) {
-            int last = -1;
-            for (int j = 0; j < 4; ++j)
-                if (ll[j]) last = max(last, scan_index(4, (lane * 4 + j) & 15, (lane * 4 + j) >> 4));
-            last = wave_max(last);
-            if (last < 0) break;
-            int prev = -1, lv = 0;
-            for (int j = 0; j < 4; ++j) {
-                const int si = scan_index(4, (lane * 4 + j) & 15, (lane * 4 + j) >> 4);
-                if (ll[j] && si < last) prev = max(prev, si);
-                if (si == last) lv = abs(ll[j]);
-            }
-            prev = wave_max(prev);
-            lv = wave_max(lv);
-            if (lv != 1 || last - prev <= kTrimGap) break;
-            for (int j = 0; j < 4; ++j)
-                if (scan_index(4, (lane * 4 + j) & 15, (lane * 4 + j) >> 4) == last) ll[j] = 0;
-        }
-        for (int cc = 0; cc < 2; ++cc) {
-            for (int it = 0; it < kTrimIters; ++it) {
-                int last = -1;
-                for (int j = 0; j < 2; ++j) {
-                    const int idx = cl * 2 + j;
-                    if (comp == cc && lc[j]) last = max(last, scan_index(3, idx & 7, idx >> 3));
-                }
-                last = wave_max(last);
-                if (last < 0) break;
-                int prev = -1, lv = 0;
-                for (int j = 0; j < 2; ++j) {
-                    const int idx = cl * 2 + j, si = scan_index(3, idx & 7, idx >> 3);
-                    if (comp == cc && lc[j] && si < last) prev = max(prev, si);
-                    if (comp == cc && si == last) lv = abs(lc[j]);
-                }
-                prev = wave_max(prev);
-                lv = wave_max(lv);
-                if (lv != 1 || last - prev <= kTrimGap) break;
-                for (int j = 0; j < 2; ++j) {
-                    const int idx = cl * 2 + j;
-                    if (comp == cc && scan_index(3, idx & 7, idx >> 3) == last) lc[j] = 0;
-                }
-            }
-        }
-    }
-    nzl = nzc = 0;
     int lbits = 0, cbits = 0;  // tu_bits_est terms of this lane's levels
+    uint32_t csl = 0, csc = 0;
     if (valid) {
-        for (int j = 0; j < 4; ++j) {
-            const int idx = lane * 4 + j, k2 = idx >> 4, k = idx & 15;
-            const int l = ll[j];
-            if (l) lbits += 4 + 2 * (31 - __builtin_clz((uint32_t)abs(l)));
-            const int si = scan_index(4, k, k2);
-            coef[si] = (int16_t)l;
-            bT[k * 16 + k2] = (int16_t)dequant_coef(l, qp, 4);
-            if (l) {
-                ++nzl;
-                lastl = si > lastl ? si : lastl;
-                csl |= 1u << (si >> 4);
+        tu_store_dequant<4, 4>(t, ul, qp, ll, sil, coef, nzl, lbits);
+        tu_store_dequant<3, 2>(t, uc, qpc, lc, sic, coef + 256 + comp * 64, nzc, cbits);
+        for (int j = 0; j < 4; ++j)
+            if (ll[j]) {
+                lastl = max(lastl, sil[j]);
+                csl |= 1u << (sil[j] >> 4);
             }
-        }
-        for (int j = 0; j < 2; ++j) {
-            const int idx = cl * 2 + j, k2 = idx >> 3, k = idx & 7;
-            const int l = lc[j];
-            if (l) cbits += 4 + 2 * (31 - __builtin_clz((uint32_t)abs(l)));
-            const int si = scan_index(3, k, k2);
-            coef[256 + comp * 64 + si] = (int16_t)l;
-            bT[256 + comp * 64 + k * 8 + k2] = (int16_t)dequant_coef(l, qpc, 3);
-            if (l) {
-                ++nzc;
-                lastc = si > lastc ? si : lastc;
-                csc |= 1u << (si >> 4);
+        for (int j = 0; j < 2; ++j)
+            if (lc[j]) {
+                lastc = max(lastc, sic[j]);
+                csc |= 1u << (sic[j] >> 4);
             }
-        }
     }
     out.nz[0] = wave_sum(nzl);
     out.last[0] = wave_max(lastl);
@@ -281,55 +116,30 @@ __device__ __forceinline__ TuResult code_tus(TuBuf& t, const Mats& M, int qp, in
         out.bits = (uint32_t)((out.nz[0] ? bl + 4 : 1) + (out.nz[1] ? bcb + 4 : 1) + (out.nz[2] ? bcr + 4 : 1));
         out.bits_y = (uint32_t)(out.nz[0] ? bl + 4 : 1);
     }
-    tu_sync<kInterCu>();
-    // ---- inverse stage 1 (columns): a[y][x] = clip16((sum_k T[k][y] b[k][x] + 64) >> 7)
+    wave_lds_sync();
     if (valid) {
-        for (int j = 0; j < 4; ++j) {
-            const int idx = lane * 4 + j, y = idx >> 4, x = idx & 15;
-            const int s = dot16(M.tt16 + y * 16, bT + x * 16);
-            a16[idx] = (int16_t)clip16((s + 64) >> 7);
-        }
-        for (int j = 0; j < 2; ++j) {
-            const int idx = cl * 2 + j, y = idx >> 3, x = idx & 7;
-            const int s = dot8(M.tt8 + y * 8, bT + 256 + comp * 64 + x * 8);
-            a16[256 + comp * 64 + idx] = (int16_t)clip16((s + 64) >> 7);
-        }
+        tu_inv_cols<4, 4>(t, M, ul);
+        tu_inv_cols<3, 2>(t, M, uc);
     }
-    tu_sync<kInterCu>();
-    // ---- inverse stage 2 (rows) + reconstruction
+    wave_lds_sync();
     int sy = 0, sc = 0, sf = 0, syf = 0;
     if (valid) {
-        const int y = lane >> 2, xb = (lane & 3) * 4;
-        uint32_t packed = 0;
-        for (int j = 0; j < 4; ++j) {
-            const int x = xb + j;
-            const int s = dot16(M.tt16 + x * 16, a16 + y * 16);
-            const int r = out.nz[0] ? (s + 2048) >> 12 : 0;
-            const int p = t.pred[y * 16 + x];
-            const int v = clip255(p + r);
-            const int e = p + t.res[y * 16 + x] - v;
-            sy += (x0 + x < disp_w && y0 + y < disp_h) ? e * e : 0;
-            sf += e * e;
-            syf += e * e;
-            packed |= (uint32_t)v << (8 * j);
-            if (!kInterCu) t.pred[y * 16 + x] = (uint8_t)v;  // intra: reconstruction stays readable in LDS
-        }
-        *reinterpret_cast<uint32_t*>(rec_y + (size_t)(y0 + y) * pitch_y + x0 + xb) = packed;
-        const int nzcomp = comp ? out.nz[2] : out.nz[1];
-        for (int j = 0; j < 2; ++j) {
-            const int idx = cl * 2 + j, yy = idx >> 3, x = idx & 7;
-            const int s = dot8(M.tt8 + x * 8, a16 + 256 + comp * 64 + yy * 8);
-            const int r = nzcomp ? (s + 2048) >> 12 : 0;
-            const int o = 256 + comp * 64 + idx;
-            const int p = t.pred[o];
-            const int v = clip255(p + r);
-            const int e = p + t.res[o] - v;
+        uint32_t packed = 0;  // the lane's 4 luma samples: row lane >> 2, columns (lane & 3) * 4 ..
+        tu_inv_rows_rec<4, 4>(t, M, ul, out.nz[0] != 0, [&](int y, int x, int o, int v, int e2) {
+            sy += (x0 + x < disp_w && y0 + y < disp_h) ? e2 : 0;
+            sf += e2;
+            syf += e2;
+            packed |= (uint32_t)v << (8 * (x & 3));
+            if (!kInterCu) t.pred[o] = (uint8_t)v;  // intra: reconstruction stays readable in LDS
+        });
+        *reinterpret_cast<uint32_t*>(rec_y + (size_t)(y0 + (lane >> 2)) * pitch_y + x0 + (lane & 3) * 4) = packed;
+        tu_inv_rows_rec<3, 2>(t, M, uc, (comp ? out.nz[2] : out.nz[1]) != 0, [&](int y, int x, int o, int v, int e2) {
             if (!kInterCu) t.pred[o] = (uint8_t)v;
-            const int xc = x0 / 2 + x, yc = y0 / 2 + yy;
-            sc += (2 * xc < disp_w && 2 * yc < disp_h) ? e * e : 0;
-            sf += e * e;
+            const int xc = x0 / 2 + x, yc = y0 / 2 + y;
+            sc += (2 * xc < disp_w && 2 * yc < disp_h) ? e2 : 0;
+            sf += e2;
             rec_uv[(size_t)yc * pitch_y + 2 * xc + comp] = (uint8_t)v;
-        }
+        });
     }
     out.sse[0] = wave_sum(sy);
     out.sse[1] = wave_sum(comp == 0 ? sc : 0);
@@ -339,11 +149,6 @@ __device__ __forceinline__ TuResult code_tus(TuBuf& t, const Mats& M, int qp, in
     return out;
 }
 
-// The split transform tree of an inter CU (split_encode / tu_encode_t of the CPU encoder,
-// same integer stages), computed by the whole wave: luma TU k = lanes 16k..16k+15 with 4
-// coefficients each, chroma TU (comp, k) = lanes 8(4comp+k).. with 2 each; decimation and
-// the trailing trim per TU through segmented shuffle reductions.  Levels go to lv (CU
-// layout), the reconstruction to rec (TuBuf layout); t.a / t.b are the stage buffers.
 // cu_summarise (hevc_core.h) of a split transform tree, by the whole wave: one ballot per
 // luma TU (lane = scan index) and one per chroma component (lane = 16 * TU + scan index) give
 // the coded masks, the rest is scalar (lane 0 alone walking 384 LDS levels cost ~1,100 VALU).
@@ -423,126 +228,36 @@ struct SplitResult {
     int node_sse[4], node_disp[4], node_lv[4];
     uint32_t node_bits[4];
 };
+// The split transform tree of an inter CU (split_encode / tu_encode_t of the CPU encoder), by
+// the whole wave: 8x8 luma TU k on lanes 16k .. 16k+15 (4 coefficients each), 4x4 chroma TU
+// (comp, k) on lanes 8 (4 comp + k) .. (2 each).  Levels go to lv (CU layout), the
+// reconstruction to rec (TuBuf layout).
 __device__ __forceinline__ SplitResult split_tus(TuBuf& t, const Mats& M, int qp, int qpc, bool valid, int16_t* lv,
                                                 uint8_t* rec, int x0, int y0, int disp_w, int disp_h) {
     const int lane = threadIdx.x & 63;
-    const int tk = lane >> 4, lbx = (tk & 1) * 8, lby = (tk >> 1) * 8, lbase = 64 * tk;  // luma TU of the lane
-    const int ct = lane >> 3, comp = ct >> 2, ck = ct & 3;                                 // chroma TU of the lane
-    const int cbx = (ck & 1) * 4, cby = (ck >> 1) * 4, cbase = 256 + 64 * comp + 16 * ck;
-    // int16 stage views with the layouts of code_tus (aT[k][y], bT[x][k], a16[y][x] per TU)
-    int16_t* aT = reinterpret_cast<int16_t*>(t.a);
-    int16_t* a16 = reinterpret_cast<int16_t*>(t.a);
-    int16_t* bT = reinterpret_cast<int16_t*>(t.b);
-    // ---- forward stage 1 (rows)
+    const int tk = lane >> 4, lbx = (tk & 1) * 8, lby = (tk >> 1) * 8;  // luma TU of the lane
+    const int ct = lane >> 3, comp = ct >> 2, ck = ct & 3;              // chroma TU of the lane
+    const int cbx = (ck & 1) * 4, cby = (ck >> 1) * 4;
+    const TuAt ul = {lby * 16 + lbx, 16, 64 * tk};
+    const TuAt uc = {256 + comp * 64 + cby * 8 + cbx, 8, 256 + 64 * comp + 16 * ck};
     if (valid) {
-        for (int j = 0; j < 4; ++j) {
-            const int idx = (lane & 15) * 4 + j, y = idx >> 3, k = idx & 7;
-            const int s = dot8(M.t8 + k * 8, t.res + (lby + y) * 16 + lbx);
-            aT[lbase + k * 8 + y] = (int16_t)((s + 2) >> 2);
-        }
-        for (int j = 0; j < 2; ++j) {
-            const int idx = (lane & 7) * 2 + j, y = idx >> 2, k = idx & 3;
-            const int s = dot4(M.t4 + k * 4, t.res + 256 + comp * 64 + (cby + y) * 8 + cbx);
-            aT[cbase + k * 4 + y] = (int16_t)((s + 1) >> 1);
-        }
+        tu_fwd_rows<3, 4>(t, M, ul);
+        tu_fwd_rows<2, 2>(t, M, uc);
     }
     wave_lds_sync();
-    // ---- forward stage 2 (columns) + quantisation
-    int ll[4] = {0, 0, 0, 0}, lc[2] = {0, 0};
-    int sil[4], sic[2];
+    int ll[4] = {0, 0, 0, 0}, lc[2] = {0, 0}, sil[4] = {0, 0, 0, 0}, sic[2] = {0, 0};
     if (valid) {
-        for (int j = 0; j < 4; ++j) {
-            const int idx = (lane & 15) * 4 + j, k2 = idx >> 3, k = idx & 7;
-            const int s = dot8(M.t8 + k2 * 8, aT + lbase + k * 8);
-            ll[j] = quant_coef((s + 256) >> 9, qp, 3, false);
-            sil[j] = scan_index(3, k, k2);
-        }
-        for (int j = 0; j < 2; ++j) {
-            const int idx = (lane & 7) * 2 + j, k2 = idx >> 2, k = idx & 3;
-            const int s = dot4(M.t4 + k2 * 4, aT + cbase + k * 4);
-            lc[j] = quant_coef((s + 128) >> 8, qpc, 2, false);
-            sic[j] = scan_index(2, k, k2);
-        }
-    } else {
-        for (int j = 0; j < 4; ++j) sil[j] = 0;
-        for (int j = 0; j < 2; ++j) sic[j] = 0;
+        tu_fwd_cols_quant<3, 4>(t, M, ul, qp, false, ll, sil);
+        tu_fwd_cols_quant<2, 2>(t, M, uc, qpc, false, lc, sic);
     }
-    // ---- decimation per TU
-    {
-        int nz = 0, mx = 0;
-        for (int j = 0; j < 4; ++j) {
-            nz += ll[j] != 0;
-            mx = max(mx, abs(ll[j]));
-        }
-        if (tu_decimate(3, false, gsum<16>(nz), gmax<16>(mx)))
-            for (int j = 0; j < 4; ++j) ll[j] = 0;
-        nz = mx = 0;
-        for (int j = 0; j < 2; ++j) {
-            nz += lc[j] != 0;
-            mx = max(mx, abs(lc[j]));
-        }
-        if (tu_decimate(2, false, gsum<8>(nz), gmax<8>(mx)))
-            for (int j = 0; j < 2; ++j) lc[j] = 0;
-    }
-    // ---- trailing isolated +-1 trim per TU (tu_encode_t rule; a stopped TU stays stopped)
-    {
-        bool on_l = true, on_c = true;
-        for (int it = 0; it < kTrimIters; ++it) {
-            int last = -1;
-            for (int j = 0; j < 4; ++j)
-                if (ll[j]) last = max(last, sil[j]);
-            last = gmax<16>(last);
-            int prev = -1, lvv = 0;
-            for (int j = 0; j < 4; ++j) {
-                if (ll[j] && sil[j] < last) prev = max(prev, sil[j]);
-                if (ll[j] && sil[j] == last) lvv = abs(ll[j]);
-            }
-            prev = gmax<16>(prev);
-            lvv = gmax<16>(lvv);
-            if (last < 0 || lvv != 1 || last - prev <= kTrimGap) on_l = false;
-            if (on_l)
-                for (int j = 0; j < 4; ++j)
-                    if (sil[j] == last) ll[j] = 0;
-            int lastc = -1;
-            for (int j = 0; j < 2; ++j)
-                if (lc[j]) lastc = max(lastc, sic[j]);
-            lastc = gmax<8>(lastc);
-            int prevc = -1, lvc = 0;
-            for (int j = 0; j < 2; ++j) {
-                if (lc[j] && sic[j] < lastc) prevc = max(prevc, sic[j]);
-                if (lc[j] && sic[j] == lastc) lvc = abs(lc[j]);
-            }
-            prevc = gmax<8>(prevc);
-            lvc = gmax<8>(lvc);
-            if (lastc < 0 || lvc != 1 || lastc - prevc <= kTrimGap) on_c = false;
-            if (on_c)
-                for (int j = 0; j < 2; ++j)
-                    if (sic[j] == lastc) lc[j] = 0;
-        }
-    }
-    // ---- levels, dequantised values, per-TU counts and bit estimates
-    int nzl = 0, nzc = 0, bl = 0, bc = 0;
+    tu_decimate_group<16>(ll, 3, false);
+    tu_trim_group<16>(ll, sil);
+    tu_decimate_group<8>(lc, 2, false);
+    tu_trim_group<8>(lc, sic);
+    int nzl = 0, nzc = 0, bl = 0, bc = 0;  // per TU: levels coded, their level_bits
     if (valid) {
-        for (int j = 0; j < 4; ++j) {
-            const int idx = (lane & 15) * 4 + j, k2 = idx >> 3, k = idx & 7;
-            const int l = ll[j];
-            lv[lbase + sil[j]] = (int16_t)l;
-            bT[lbase + k * 8 + k2] = (int16_t)dequant_coef(l, qp, 3);
-            if (l) {
-                ++nzl;
-                bl += 4 + 2 * (31 - __builtin_clz((uint32_t)abs(l)));
-            }
-        }
-        for (int j = 0; j < 2; ++j) {
-            const int idx = (lane & 7) * 2 + j, k2 = idx >> 2, k = idx & 3;
-            const int l = lc[j];
-            lv[cbase + sic[j]] = (int16_t)l;
-            bT[cbase + k * 4 + k2] = (int16_t)dequant_coef(l, qpc, 2);
-            if (l) {
-                ++nzc;
-                bc += 4 + 2 * (31 - __builtin_clz((uint32_t)abs(l)));
-            }
-        }
+        tu_store_dequant<3, 4>(t, ul, qp, ll, sil, lv + ul.buf, nzl, bl);
+        tu_store_dequant<2, 2>(t, uc, qpc, lc, sic, lv + uc.buf, nzc, bc);
     }
     nzl = gsum<16>(nzl);
     nzc = gsum<8>(nzc);
@@ -552,44 +267,24 @@ __device__ __forceinline__ SplitResult split_tus(TuBuf& t, const Mats& M, int qp
     out.bits = (uint32_t)wave_sum(((lane & 15) == 0 ? (nzl ? bl + 4 : 1) : 0) + ((lane & 7) == 0 ? (nzc ? bc + 4 : 1) : 0));
     out.bits_y = (uint32_t)wave_sum((lane & 15) == 0 ? (nzl ? bl + 4 : 1) : 0);
     wave_lds_sync();
-    // ---- inverse stage 1 (columns)
     if (valid) {
-        for (int j = 0; j < 4; ++j) {
-            const int idx = (lane & 15) * 4 + j, y = idx >> 3, x = idx & 7;
-            const int s = dot8(M.tt8 + y * 8, bT + lbase + x * 8);
-            a16[lbase + idx] = (int16_t)clip16((s + 64) >> 7);
-        }
-        for (int j = 0; j < 2; ++j) {
-            const int idx = (lane & 7) * 2 + j, y = idx >> 2, x = idx & 3;
-            const int s = dot4(M.tt4 + y * 4, bT + cbase + x * 4);
-            a16[cbase + idx] = (int16_t)clip16((s + 64) >> 7);
-        }
+        tu_inv_cols<3, 4>(t, M, ul);
+        tu_inv_cols<2, 2>(t, M, uc);
     }
     wave_lds_sync();
-    // ---- inverse stage 2 (rows) + reconstruction
     int sf = 0, sy = 0, sc = 0, syf = 0;
     if (valid) {
-        for (int j = 0; j < 4; ++j) {
-            const int idx = (lane & 15) * 4 + j, y = idx >> 3, x = idx & 7;
-            const int s = dot8(M.tt8 + x * 8, a16 + lbase + y * 8);
-            const int r = nzl ? (s + 2048) >> 12 : 0;
-            const int o = (lby + y) * 16 + lbx + x, p = t.pred[o];
-            const int v = clip255(p + r), e = p + t.res[o] - v;
-            sf += e * e;
-            syf += e * e;
-            sy += (x0 + lbx + x < disp_w && y0 + lby + y < disp_h) ? e * e : 0;
+        tu_inv_rows_rec<3, 4>(t, M, ul, nzl != 0, [&](int y, int x, int o, int v, int e2) {
+            sf += e2;
+            syf += e2;
+            sy += (x0 + lbx + x < disp_w && y0 + lby + y < disp_h) ? e2 : 0;
             rec[o] = (uint8_t)v;
-        }
-        for (int j = 0; j < 2; ++j) {
-            const int idx = (lane & 7) * 2 + j, y = idx >> 2, x = idx & 3;
-            const int s = dot4(M.tt4 + x * 4, a16 + cbase + y * 4);
-            const int r = nzc ? (s + 2048) >> 12 : 0;
-            const int o = 256 + comp * 64 + (cby + y) * 8 + cbx + x, p = t.pred[o];
-            const int v = clip255(p + r), e = p + t.res[o] - v;
-            sf += e * e;
-            sc += (2 * (x0 / 2 + cbx + x) < disp_w && 2 * (y0 / 2 + cby + y) < disp_h) ? e * e : 0;
+        });
+        tu_inv_rows_rec<2, 2>(t, M, uc, nzc != 0, [&](int y, int x, int o, int v, int e2) {
+            sf += e2;
+            sc += (2 * (x0 / 2 + cbx + x) < disp_w && 2 * (y0 / 2 + cby + y) < disp_h) ? e2 : 0;
             rec[o] = (uint8_t)v;
-        }
+        });
     }
     out.sse_full = wave_sum(sf);
     out.sse_y_full = wave_sum(syf);
@@ -611,100 +306,43 @@ __device__ __forceinline__ SplitResult split_tus(TuBuf& t, const Mats& M, int qp
 }
 
 // The 4x4 option of the split tree's luma nodes (split_encode's try4 on the CPU), whole wave: 4x4
-// TU j16 = lane >> 2 (node k = j16 >> 2, TU j = j16 & 3 in z order), lane l4 = lane & 3 takes row l4
-// of the forward row stage, column l4 of the column stage and row l4 of both inverse stages;
-// decimation and the trailing trim per TU over its 4 lanes (tu_encode_t<2> rules).  Levels to lv4
-// (node k TU j at 64k + 16j, scan order), reconstruction to rec4 (16x16 luma, TuBuf layout);
-// per-node SSE (node / display area) and bits in the result.
+// TU j16 = lane >> 2 (node k = j16 >> 2, TU j = j16 & 3 in z order) on 4 lanes with 4 coefficients
+// each (tu_encode_t<2> rules).  Levels to lv4 (node k TU j at 64k + 16j, scan order),
+// reconstruction to rec4 (16x16 luma, TuBuf layout); per-node SSE (node / display area) and bits
+// in the result.
 struct Split4Result {
     int node_sse[4], node_disp[4];
     uint32_t node_bits[4];
 };
 __device__ __forceinline__ Split4Result split4_luma(TuBuf& t, const Mats& M, int qp, bool valid, int16_t* lv4,
                                                     uint8_t* rec4, int x0, int y0, int disp_w, int disp_h) {
-    const int lane = threadIdx.x & 63, j16 = lane >> 2, l4 = lane & 3;
+    const int lane = threadIdx.x & 63, j16 = lane >> 2;
     const int k = j16 >> 2, j = j16 & 3;
     const int tx = (k & 1) * 8 + (j & 1) * 4, ty = (k >> 1) * 8 + (j >> 1) * 4;  // TU origin in the CU
-    const int base = 16 * j16;
-    int16_t* aT = reinterpret_cast<int16_t*>(t.a);
-    int16_t* a16 = reinterpret_cast<int16_t*>(t.a);
-    int16_t* bT = reinterpret_cast<int16_t*>(t.b);
-    if (valid)  // forward stage 1 (rows): row l4, outputs kk
-        for (int kk = 0; kk < 4; ++kk) {
-            const int s = dot4(M.t4 + kk * 4, t.res + (ty + l4) * 16 + tx);
-            aT[base + kk * 4 + l4] = (int16_t)((s + 1) >> 1);
-        }
+    const TuAt u = {ty * 16 + tx, 16, 16 * j16};
+    if (valid) tu_fwd_rows<2, 4>(t, M, u);
     wave_lds_sync();
     int ll[4] = {0, 0, 0, 0}, si[4] = {0, 0, 0, 0};
-    if (valid)  // forward stage 2 (columns): column kk = l4, vertical frequency k2
-        for (int k2 = 0; k2 < 4; ++k2) {
-            const int s = dot4(M.t4 + k2 * 4, aT + base + l4 * 4);
-            ll[k2] = quant_coef((s + 128) >> 8, qp, 2, false);
-            si[k2] = scan_index(2, l4, k2);
-        }
-    {  // decimation per TU
-        int nz = 0, mx = 0;
-        for (int q = 0; q < 4; ++q) {
-            nz += ll[q] != 0;
-            mx = max(mx, abs(ll[q]));
-        }
-        if (tu_decimate(2, false, gsum<4>(nz), gmax<4>(mx)))
-            for (int q = 0; q < 4; ++q) ll[q] = 0;
-    }
-    {  // trailing isolated +-1 trim per TU (a stopped TU stays stopped)
-        bool on = true;
-        for (int it = 0; it < kTrimIters; ++it) {
-            int last = -1;
-            for (int q = 0; q < 4; ++q)
-                if (ll[q]) last = max(last, si[q]);
-            last = gmax<4>(last);
-            int prev = -1, lvv = 0;
-            for (int q = 0; q < 4; ++q) {
-                if (ll[q] && si[q] < last) prev = max(prev, si[q]);
-                if (ll[q] && si[q] == last) lvv = abs(ll[q]);
-            }
-            prev = gmax<4>(prev);
-            lvv = gmax<4>(lvv);
-            if (last < 0 || lvv != 1 || last - prev <= kTrimGap) on = false;
-            if (on)
-                for (int q = 0; q < 4; ++q)
-                    if (si[q] == last) ll[q] = 0;
-        }
-    }
+    if (valid) tu_fwd_cols_quant<2, 4>(t, M, u, qp, false, ll, si);
+    tu_decimate_group<4>(ll, 2, false);
+    tu_trim_group<4>(ll, si);
     int nz = 0, bl = 0;
-    if (valid)
-        for (int k2 = 0; k2 < 4; ++k2) {
-            const int l = ll[k2];
-            lv4[64 * k + 16 * j + si[k2]] = (int16_t)l;
-            bT[base + l4 * 4 + k2] = (int16_t)dequant_coef(l, qp, 2);
-            if (l) {
-                ++nz;
-                bl += 4 + 2 * (31 - __builtin_clz((uint32_t)abs(l)));
-            }
-        }
+    if (valid) tu_store_dequant<2, 4>(t, u, qp, ll, si, lv4 + u.buf, nz, bl);
     nz = gsum<4>(nz);
     bl = gsum<4>(bl);
     wave_lds_sync();
-    if (valid)  // inverse stage 1 (columns): row y = l4 of the intermediate
-        for (int x = 0; x < 4; ++x) {
-            const int s = dot4(M.tt4 + l4 * 4, bT + base + x * 4);
-            a16[base + l4 * 4 + x] = (int16_t)clip16((s + 64) >> 7);
-        }
+    if (valid) tu_inv_cols<2, 4>(t, M, u);
     wave_lds_sync();
     int sf = 0, sd = 0;
-    if (valid)  // inverse stage 2 (rows) + reconstruction: row l4
-        for (int x = 0; x < 4; ++x) {
-            const int s = dot4(M.tt4 + x * 4, a16 + base + l4 * 4);
-            const int r = nz ? (s + 2048) >> 12 : 0;
-            const int o = (ty + l4) * 16 + tx + x, p = t.pred[o];
-            const int v = clip255(p + r), e = p + t.res[o] - v;
-            sf += e * e;
-            sd += (x0 + tx + x < disp_w && y0 + ty + l4 < disp_h) ? e * e : 0;
+    if (valid)
+        tu_inv_rows_rec<2, 4>(t, M, u, nz != 0, [&](int y, int x, int o, int v, int e2) {
+            sf += e2;
+            sd += (x0 + tx + x < disp_w && y0 + ty + y < disp_h) ? e2 : 0;
             rec4[o] = (uint8_t)v;
-        }
+        });
     Split4Result out;
     const int gs = gsum<16>(sf), gd = gsum<16>(sd);
-    const int gb = gsum<16>(l4 == 0 ? (nz ? bl + 4 : 1) : 0);  // the node's four TUs
+    const int gb = gsum<16>((lane & 3) == 0 ? (nz ? bl + 4 : 1) : 0);  // the node's four TUs
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
         out.node_sse[q] = __builtin_amdgcn_readlane(gs, 16 * q);
@@ -862,8 +500,8 @@ __global__ __launch_bounds__(256) void k_hevc_inter(Geometry g, const HevcFrameS
     wave_lds_sync();  // from here on every wave works alone (wave-local syncs, per-wave LDS)
     int16_t* co = coef + (size_t)(valid ? i : 0) * kCoefPerCu;
     // option 1, one 16x16 luma TU (writes its levels and reconstruction; t.pred keeps the prediction)
-    const TuResult r = code_tus<true>(t, M, qp, qpc, false, valid, co, fs->rec_y, g.pitch, fs->rec_uv, x0, y0,
-                                      g.width, g.height);
+    const TuResult r = code_tus<true>(t, M, qp, qpc, valid, co, fs->rec_y, g.pitch, fs->rec_uv, x0, y0, g.width,
+                                      g.height);
     // option 2, the split transform tree (split_encode of the CPU encoder), whole wave -- only
     // when option 1 coded something (split_worth_trying, as the CPU encoder)
     const bool try_split = fs->tu_split != 0 && valid && split_worth_trying(r.nz[0] + r.nz[1] + r.nz[2]);  // wave-uniform
@@ -1617,8 +1255,7 @@ __device__ SplitIntraResult split_intra_code(TuBuf& t, SplitRefs& S, const Intra
     uint32_t bits = 0;
 #pragma unroll
     for (int j = 0; j < 6; ++j) {
-        const int l = lv[64 * j + lane], a = l < 0 ? -l : l;
-        const int b = a ? 4 + 2 * (31 - __builtin_clz((uint32_t)a)) : 0;
+        const int a = lv[64 * j + lane], b = level_bits(a);
         if (j < 4 && !(kTu4 && ((tu4 >> j) & 1))) {
             const int sum = wave_sum(b);
             bits += (uint32_t)(__ballot(a != 0) ? sum + 4 : 1);
@@ -1807,7 +1444,7 @@ __global__ __launch_bounds__(64 * kMaxSliceRows) void k_hevc_intra(Geometry g, c
                 t.res[256 + comp * 64 + rc * 8 + cc] = (int16_t)((int)((sc2 >> (8 * comp)) & 0xff) - p);
             }
             wave_lds_sync();
-            const TuResult res = code_tus<false>(t, M, qp, qpc, true, true, coef + (size_t)i * kCoefPerCu, fs->rec_y,
+            const TuResult res = code_tus<false>(t, M, qp, qpc, true, coef + (size_t)i * kCoefPerCu, fs->rec_y,
                                                  g.pitch, fs->rec_uv, x0, y0, g.width, g.height);
             acc[0] += (unsigned)res.sse[0];
             acc[1] += (unsigned)res.sse[1];

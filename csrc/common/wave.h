@@ -33,20 +33,25 @@ __device__ __forceinline__ uint32_t rows_sum(uint32_t v) {
 // Wave sum / max / or, every lane gets it (called with the whole wave active): quad and row-of-16
 // steps with DPP (quad_perm [1,0,3,2], [2,3,0,1], row_ror 4, row_ror 8), then the four rows with the
 // two permlane swaps -- all VALU, no LDS latency on the (often serial) reduction chains.
-__device__ __forceinline__ int wave_sum(int v) {
+// row16_sum / row16_max are the DPP steps alone: the lane's row of 16.
+__device__ __forceinline__ int row16_sum(int v) {
     v += __builtin_amdgcn_mov_dpp(v, 0xB1, 0xF, 0xF, false);
     v += __builtin_amdgcn_mov_dpp(v, 0x4E, 0xF, 0xF, false);
     v += __builtin_amdgcn_mov_dpp(v, 0x124, 0xF, 0xF, false);
     v += __builtin_amdgcn_mov_dpp(v, 0x128, 0xF, 0xF, false);
-    return (int)rows_sum((uint32_t)v);
+    return v;
 }
-__device__ __forceinline__ int wave_max(int v) {
+__device__ __forceinline__ int row16_max(int v) {
     v = max(v, __builtin_amdgcn_mov_dpp(v, 0xB1, 0xF, 0xF, false));
     v = max(v, __builtin_amdgcn_mov_dpp(v, 0x4E, 0xF, 0xF, false));
     v = max(v, __builtin_amdgcn_mov_dpp(v, 0x124, 0xF, 0xF, false));
     v = max(v, __builtin_amdgcn_mov_dpp(v, 0x128, 0xF, 0xF, false));
+    return v;
+}
+__device__ __forceinline__ int wave_sum(int v) { return (int)rows_sum((uint32_t)row16_sum(v)); }
+__device__ __forceinline__ int wave_max(int v) {
     uint32_t a, b;
-    xrow16((uint32_t)v, a, b);
+    xrow16((uint32_t)row16_max(v), a, b);
     v = max((int)a, (int)b);
     xrow32((uint32_t)v, a, b);
     return max((int)a, (int)b);
@@ -85,6 +90,36 @@ __device__ __forceinline__ int qbc(int v) {
     return __builtin_amdgcn_mov_dpp(v, K * 0x55, 0xF, 0xF, false);
 }
 __device__ __forceinline__ int quad_sum(int v) { return qbc<0>(v) + qbc<1>(v) + qbc<2>(v) + qbc<3>(v); }
+
+// Sum / max inside aligned groups of G lanes (G a power of two), every lane gets its group's value
+// (whole wave active): an xor-shuffle ladder for G <= 16, the DPP steps of wave_sum / wave_max and
+// the xor-16 swap for G = 32, wave_sum / wave_max themselves for G = 64.
+template <int G>
+__device__ __forceinline__ int gsum(int v) {
+    if constexpr (G == 64) {
+        return wave_sum(v);
+    } else if constexpr (G == 32) {
+        uint32_t a, b;
+        xrow16((uint32_t)row16_sum(v), a, b);
+        return (int)(a + b);
+    } else {
+        for (int o = G / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+        return v;
+    }
+}
+template <int G>
+__device__ __forceinline__ int gmax(int v) {
+    if constexpr (G == 64) {
+        return wave_max(v);
+    } else if constexpr (G == 32) {
+        uint32_t a, b;
+        xrow16((uint32_t)row16_max(v), a, b);
+        return max((int)a, (int)b);
+    } else {
+        for (int o = G / 2; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
+        return v;
+    }
+}
 
 // Inclusive prefix sum over the wave's lanes.
 __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v) {

@@ -264,7 +264,7 @@ def test_gpu_hevc_tu_split_bit_exact_vs_cpu(gpu, w, h, qp):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("w,h,qp,desktop", [(64, 48, 26, False), (160, 96, 30, False), (320, 192, 28, True),
-                                            (1920, 1080, 34, True)])
+                                            (1920, 1080, 34, True), (100, 60, 38, False)])
 def test_gpu_hevc_4x4_luma_tus_bit_exact_vs_cpu(gpu, w, h, qp, desktop):
     """tu_split 2 on the GPU (split4_luma: sixteen 4x4 luma TUs on 4 lanes each, per-node SSE +
     lambda * bits choice against the 8x8 TU) == the CPU encoder, bit for bit; decoded ==
@@ -391,7 +391,7 @@ def test_cpu_hevc_intra_split_decodes_to_reconstruction(native, qp):
     assert dec0.stats.get("tu_split", 0) == 0
 
 
-@pytest.mark.parametrize("w,h,qp", [(64, 48, 26), (160, 96, 30), (320, 192, 34)])
+@pytest.mark.parametrize("w,h,qp", [(64, 48, 26), (160, 96, 30), (320, 192, 34), (100, 60, 38)])
 def test_cpu_hevc_4x4_luma_tus_decode_to_reconstruction(native, w, h, qp):
     """tu_split 2: 8x8 luma nodes of split inter trees may code four 4x4 TUs (split_transform_flag
     at the 8x8 node, cbf_luma and cu_qp_delta per 4x4 TU, the node's chroma after the fourth) --
