@@ -190,6 +190,8 @@ PYBIND11_MODULE(_native, m) {
         .def_readwrite("intra_in_p", &h264::EncoderConfig::intra_in_p)
         .def_readwrite("vp8_bpred", &h264::EncoderConfig::vp8_bpred)
         .def_readwrite("vp8_intra", &h264::EncoderConfig::vp8_intra)
+        .def_readwrite("vp8_tokens", &h264::EncoderConfig::vp8_tokens)
+        .def_readwrite("vp8_tokens_cap", &h264::EncoderConfig::vp8_tokens_cap)
         .def_readwrite("mask_x0", &h264::EncoderConfig::mask_x0)
         .def_readwrite("mask_y0", &h264::EncoderConfig::mask_y0)
         .def_readwrite("mask_x1", &h264::EncoderConfig::mask_x1)
@@ -373,6 +375,8 @@ PYBIND11_MODULE(_native, m) {
              py::arg("config"), py::arg("stream") = 0)
         .def_property_readonly("pitch", &vp8::GpuVp8Encoder::pitch)
         .def_property_readonly("coded_height", [](vp8::GpuVp8Encoder& e) { return e.geometry().coded_h; })
+        .def_property_readonly("gpu_tokens", &vp8::GpuVp8Encoder::gpu_tokens)
+        .def_property_readonly("token_fallbacks", &vp8::GpuVp8Encoder::token_fallbacks)
         .def(
             "encode",
             [](vp8::GpuVp8Encoder& e, uintptr_t y, uintptr_t uv, bool force_idr) {
@@ -958,6 +962,13 @@ PYBIND11_MODULE(_native, m) {
                                        copy_plane(s.encoder().recon_uv(), g.pitch, g.coded_w, g.coded_h / 2));
              })
         .def_property_readonly("stats", [](Session& s) { return s.encoder().last_stats(); })
+        .def_property_readonly("vp8_tokens", [](Session& s) -> py::object {
+            // VP8 only (else None): who codes the token partitions as the encoder resolved it, and
+            // the frames whose partitions outgrew their regions and were coded again on the host
+            auto* e = dynamic_cast<vp8::GpuVp8Encoder*>(&s.encoder());
+            if (!e) return py::none();
+            return py::make_tuple(e->gpu_tokens() ? "gpu" : "host", e->token_fallbacks());
+        })
         .def("slice_timing",
              [](Session& s) {
                  // HEVC only: per-substream CABAC timing of the last collected picture (GpuHevcEncoder)

@@ -96,6 +96,13 @@ struct EncoderConfig {
                               // vp8_intra_candidate)
     int vp8_bpred = 1;        // VP8 key frames: macroblocks may take B_PRED (16 4x4 sub-block modes, vp8_core.h
                               // bpred_luma) when its SAD + lambda * mode bits beat the 16x16 mode's
+    // VP8 token partitions: 0 = boolean-coded by host threads, 1 = on the GPU (k_vp8_tokens: only the
+    // records and the coded partitions cross the host link), -1 = MXDESK_VP8_TOKENS (host | gpu), else
+    // host.  The stream does not depend on it.  CpuVp8Encoder ignores it.
+    int vp8_tokens = -1;
+    // vp8_tokens 1: bytes per macroblock of a token partition's rows that the GPU coder may write; a
+    // frame with a larger partition is coded again on the host (same bytes)
+    int vp8_tokens_cap = 1024;
     int tu_split = 2;         // HEVC: inter transform trees may split into 8x8 luma / 4x4 chroma TUs (1), and each
                               // 8x8 luma node again into four 4x4 TUs (2), per node by SSE + lambda * bits
     // HEVC I pictures: a 16x16 intra unit may code its transform tree as four 8x8 luma / 4x4 chroma TUs,

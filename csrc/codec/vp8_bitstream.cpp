@@ -11,16 +11,13 @@
 #include <stdexcept>
 
 #include "vp8_encoder.h"
+#include "vp8_tokens.h"
 
 namespace mx {
 namespace vp8 {
 
 namespace {
 
-inline int coef_index(int type, int band, int ctx) { return ((type * 8 + band) * 3 + ctx) * 11; }
-
-// Token coding over a probability table: Enc::tok(table index, bit) codes (or counts) a
-// context-coded token branch, Enc::fix(prob, bit) a fixed-probability bit (extra bits, sign).
 struct TokWriter {
     BoolEncoder& e;
     const uint8_t* probs;
@@ -37,86 +34,6 @@ struct TokWriterCount {  // coding + branch statistics for the next frame's prob
     }
     void fix(int prob, int bit) { e.put(prob, bit); }
 };
-
-template <class Enc>
-void put_extra(Enc& e, int v, const uint8_t* p, int n) {
-    for (int k = n - 1; k >= 0; --k) e.fix(p[n - 1 - k], (v >> k) & 1);
-}
-
-// One block's tokens (13.2 / 13.3).
-template <class Enc>
-void put_block(Enc& e, const int16_t* lv, int first, int type, int ctx) {
-    int last = 15;
-    while (last >= first && lv[last] == 0) --last;
-    if (last < first) {
-        e.tok(coef_index(type, kBand[first], ctx) + 0, 0);  // EOB
-        return;
-    }
-    bool prev_zero = false;
-    for (int i = first; i <= last; ++i) {
-        const int P = coef_index(type, kBand[i], ctx);
-        if (!prev_zero) e.tok(P + 0, 1);  // not EOB
-        const int v = lv[i], a = v < 0 ? -v : v;
-        if (a == 0) {
-            e.tok(P + 1, 0);
-            ctx = 0;
-            prev_zero = true;
-            continue;
-        }
-        e.tok(P + 1, 1);
-        if (a == 1) {
-            e.tok(P + 2, 0);
-        } else {
-            e.tok(P + 2, 1);
-            if (a <= 4) {
-                e.tok(P + 3, 0);
-                if (a == 2) {
-                    e.tok(P + 4, 0);
-                } else {
-                    e.tok(P + 4, 1);
-                    e.tok(P + 5, a == 4);
-                }
-            } else {
-                e.tok(P + 3, 1);
-                if (a <= 10) {
-                    e.tok(P + 6, 0);
-                    if (a <= 6) {
-                        e.tok(P + 7, 0);
-                        put_extra(e, a - 5, kPcat1, 1);
-                    } else {
-                        e.tok(P + 7, 1);
-                        put_extra(e, a - 7, kPcat2, 2);
-                    }
-                } else {
-                    e.tok(P + 6, 1);
-                    if (a <= 34) {
-                        e.tok(P + 8, 0);
-                        if (a <= 18) {
-                            e.tok(P + 9, 0);
-                            put_extra(e, a - 11, kPcat3, 3);
-                        } else {
-                            e.tok(P + 9, 1);
-                            put_extra(e, a - 19, kPcat4, 4);
-                        }
-                    } else {
-                        e.tok(P + 8, 1);
-                        if (a <= 66) {
-                            e.tok(P + 10, 0);
-                            put_extra(e, a - 35, kPcat5, 5);
-                        } else {
-                            e.tok(P + 10, 1);
-                            put_extra(e, a - 67, kPcat6, 11);
-                        }
-                    }
-                }
-            }
-        }
-        e.fix(128, v < 0);
-        ctx = a == 1 ? 1 : 2;
-        prev_zero = false;
-    }
-    if (last < 15) e.tok(coef_index(type, kBand[last + 1], ctx) + 0, 0);  // EOB
-}
 
 inline int nzb(const Vp8Mb& m, int b) { return (m.nz >> b) & 1; }
 
@@ -304,11 +221,17 @@ void find_near_mvs(const Vp8Mb* mbs, int mb_w, int mb_h, int mbx, int mby, int n
     }
 }
 
-void write_frame(const FrameDesc& f, const Vp8Mb* mbs, const std::function<const int16_t*(int)>& levels,
-                 std::vector<uint8_t>& out,
-                 const std::function<void(int, const std::function<void(int)>&)>& run_parallel, TokenStats* stats) {
+void plan_token_probs(const TokenStats* stats, uint8_t* upd, uint8_t* probs) {
+    if (stats && stats->valid) {
+        plan_prob_updates(reinterpret_cast<const uint32_t(*)[2]>(stats->n[0].data()), upd, probs);
+    } else {
+        std::memset(upd, 0, kNumCoefProbs);
+        std::memcpy(probs, kCoefProbs0, kNumCoefProbs);
+    }
+}
+
+void write_first_partition(const FrameDesc& f, const Vp8Mb* mbs, const uint8_t* upd, std::vector<uint8_t>& p1) {
     const int nmb = f.mb_w * f.mb_h;
-    const int nparts = 1 << f.log2_parts;
     int coded = 0, intra = 0;
     for (int i = 0; i < nmb; ++i) {
         coded += mbs[i].nz != 0;
@@ -325,18 +248,8 @@ void write_frame(const FrameDesc& f, const Vp8Mb* mbs, const std::function<const
     auto prob_of = [](int zero, int total) { return total ? std::clamp((zero * 256 + total / 2) / total, 1, 255) : 255; };
     const int seg_p[3] = {prob_of(seg_n[0] + seg_n[1], nmb), prob_of(seg_n[0], seg_n[0] + seg_n[1]),
                           prob_of(seg_n[2], seg_n[2] + seg_n[3])};
-    // ---- probability updates planned from the previous frame's branch statistics of this type
-    uint8_t upd[1056], probs[1056];
-    if (stats && stats->valid) {
-        plan_prob_updates(reinterpret_cast<const uint32_t(*)[2]>(stats->n[0].data()), upd, probs);
-    } else {
-        std::memset(upd, 0, sizeof upd);
-        std::memcpy(probs, kCoefProbs0, sizeof probs);
-    }
-    // ---- first partition (a job beside the token partitions: it reads only modes / vectors)
-    std::vector<uint8_t> p1;
     p1.reserve(16 + (size_t)nmb / 2);
-    auto code_first = [&]() {
+    {
         BoolEncoder e(p1);
         if (f.key) {
             e.literal(0, 1);  // color_space
@@ -492,7 +405,45 @@ void write_frame(const FrameDesc& f, const Vp8Mb* mbs, const std::function<const
                 put_mv_component(e, (m.mvx - near[0][0]) / 2, kMvDefault[1]);
             }
         e.flush();
-    };
+    }
+}
+
+void assemble_frame(const FrameDesc& f, const std::vector<uint8_t>& p1, const uint8_t* const* parts,
+                    const uint32_t* lens, std::vector<uint8_t>& out) {
+    const int nparts = 1 << f.log2_parts;
+    if (p1.size() >= (1u << 19)) throw std::runtime_error("vp8 writer: first partition too large");
+    // frame tag, key-frame start code + size, partition 1, partition sizes, data
+    const uint32_t tag = (f.key ? 0u : 1u) | (0u << 1) | (1u << 4) | ((uint32_t)p1.size() << 5);
+    out.push_back((uint8_t)tag);
+    out.push_back((uint8_t)(tag >> 8));
+    out.push_back((uint8_t)(tag >> 16));
+    if (f.key) {
+        const uint8_t sc[3] = {0x9d, 0x01, 0x2a};
+        out.insert(out.end(), sc, sc + 3);
+        out.push_back((uint8_t)(f.width & 0xff));
+        out.push_back((uint8_t)((f.width >> 8) & 0x3f));
+        out.push_back((uint8_t)(f.height & 0xff));
+        out.push_back((uint8_t)((f.height >> 8) & 0x3f));
+    }
+    out.insert(out.end(), p1.begin(), p1.end());
+    for (int p = 0; p + 1 < nparts; ++p) {
+        out.push_back((uint8_t)lens[p]);
+        out.push_back((uint8_t)(lens[p] >> 8));
+        out.push_back((uint8_t)(lens[p] >> 16));
+    }
+    for (int p = 0; p < nparts; ++p) out.insert(out.end(), parts[p], parts[p] + lens[p]);
+}
+
+void write_frame(const FrameDesc& f, const Vp8Mb* mbs, const std::function<const int16_t*(int)>& levels,
+                 std::vector<uint8_t>& out,
+                 const std::function<void(int, const std::function<void(int)>&)>& run_parallel, TokenStats* stats) {
+    const int nparts = 1 << f.log2_parts;
+    // ---- probability updates planned from the previous frame's branch statistics of this type
+    uint8_t upd[1056], probs[1056];
+    plan_token_probs(stats, upd, probs);
+    // ---- first partition (a job beside the token partitions: it reads only modes / vectors)
+    std::vector<uint8_t> p1;
+    auto code_first = [&]() { write_first_partition(f, mbs, upd, p1); };
     // ---- token partitions, concurrently, over the updated probabilities (counting this frame's
     // branch statistics on the way when the caller keeps them)
     std::vector<std::vector<uint8_t>> parts((size_t)nparts);
@@ -527,7 +478,6 @@ void write_frame(const FrameDesc& f, const Vp8Mb* mbs, const std::function<const
         e.flush();
     });
     if (first_err) std::rethrow_exception(first_err);
-    if (p1.size() >= (1u << 19)) throw std::runtime_error("vp8 writer: first partition too large");
     if (stats) {
         stats->n.assign(1056, std::array<uint32_t, 2>{0u, 0u});
         for (int p = 0; p < nparts; ++p)
@@ -540,27 +490,14 @@ void write_frame(const FrameDesc& f, const Vp8Mb* mbs, const std::function<const
         stats->us_tokens = 0;
         for (int p = 0; p < nparts; ++p) stats->us_tokens += job_us[(size_t)p + 1];
     }
-    // ---- assemble: frame tag, key-frame start code + size, partition 1, partition sizes, data
-    const uint32_t tag = (f.key ? 0u : 1u) | (0u << 1) | (1u << 4) | ((uint32_t)p1.size() << 5);
-    out.push_back((uint8_t)tag);
-    out.push_back((uint8_t)(tag >> 8));
-    out.push_back((uint8_t)(tag >> 16));
-    if (f.key) {
-        const uint8_t sc[3] = {0x9d, 0x01, 0x2a};
-        out.insert(out.end(), sc, sc + 3);
-        out.push_back((uint8_t)(f.width & 0xff));
-        out.push_back((uint8_t)((f.width >> 8) & 0x3f));
-        out.push_back((uint8_t)(f.height & 0xff));
-        out.push_back((uint8_t)((f.height >> 8) & 0x3f));
+    // ---- assemble
+    const uint8_t* ptr[kMaxTokenParts];
+    uint32_t len[kMaxTokenParts];
+    for (int p = 0; p < nparts; ++p) {
+        ptr[p] = parts[(size_t)p].data();
+        len[p] = (uint32_t)parts[(size_t)p].size();
     }
-    out.insert(out.end(), p1.begin(), p1.end());
-    for (int p = 0; p + 1 < nparts; ++p) {
-        const uint32_t n = (uint32_t)parts[(size_t)p].size();
-        out.push_back((uint8_t)n);
-        out.push_back((uint8_t)(n >> 8));
-        out.push_back((uint8_t)(n >> 16));
-    }
-    for (const auto& p : parts) out.insert(out.end(), p.begin(), p.end());
+    assemble_frame(f, p1, ptr, len, out);
 }
 
 // ------------------------------------------------------------------ partition worker pool

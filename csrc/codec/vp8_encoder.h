@@ -1,13 +1,16 @@
 // VP8 encoders (RFC 6386): GpuVp8Encoder (HIP analysis -- motion search shared with H.264,
-// transforms, quantisation, reconstruction -- plus boolean-coded partitions written by host
-// threads, one per token partition) and CpuVp8Encoder (the same decisions serially; the bit-exact
-// oracle for the GPU path and the no-GPU fallback).  Selected by WEBRTC_ENCODER=vp8enc, the
+// transforms, quantisation, reconstruction -- plus boolean-coded partitions: the token partitions
+// written by host threads, one per partition, or with EncoderConfig::vp8_tokens 1 by k_vp8_tokens on
+// the GPU, one workgroup per partition, the host then writing only the first partition) and
+// CpuVp8Encoder (the same decisions serially; the bit-exact oracle for the GPU path and the no-GPU
+// fallback).  Selected by WEBRTC_ENCODER=vp8enc, the
 // reference's libvpx choice (reference README.md:21,35).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <array>
+#include <atomic>
 #include <condition_variable>
 #include <deque>
 #include <exception>
@@ -127,6 +130,15 @@ void write_frame(const FrameDesc& f, const Vp8Mb* mbs, const std::function<const
                  std::vector<uint8_t>& out,
                  const std::function<void(int, const std::function<void(int)>&)>& run_parallel,
                  TokenStats* stats = nullptr);
+// write_frame's parts, for a caller that codes the token partitions elsewhere (GpuVp8Encoder with
+// vp8_tokens 1).  The frame's coefficient probabilities probs[1056] and their updates upd[1056]
+// (0: none) from the statistics (null or not valid: the defaults, no updates):
+void plan_token_probs(const TokenStats* stats, uint8_t* upd, uint8_t* probs);
+// the first partition (frame header with the updates, per-macroblock modes and vectors):
+void write_first_partition(const FrameDesc& f, const Vp8Mb* mbs, const uint8_t* upd, std::vector<uint8_t>& p1);
+// and the frame: tag, key-frame header, first partition, partition sizes, the 1 << log2_parts partitions.
+void assemble_frame(const FrameDesc& f, const std::vector<uint8_t>& p1, const uint8_t* const* parts,
+                    const uint32_t* lens, std::vector<uint8_t>& out);
 
 // Near / nearest / best motion vectors of macroblock (mbx, mby) (RFC 6386 find_near_mvs, with
 // the decoder's clamping); every macroblock of the picture is inter (P frames).  cnt[4] out.
@@ -300,6 +312,11 @@ struct Vp8DeviceBuffers {
     h264::DeviceBuffers me;  // shared H.264 motion search (fs = &st->me, mb = vectors)
     uint8_t* icand;        // [nmb] inter frames' intra pass: candidate << 7 | best 16x16 mode
     int* ilist;            // [1 + nmb] the intra pass's candidates: count, then macroblock indices
+    // vp8_tokens 1: k_vp8_tokens' mapped host block (vp8_tokens.h: Vp8TokenHeader with the frame's
+    // probabilities in and the lengths out, the partitions' branch counts, their byte regions of
+    // tok_region bytes each); else null
+    uint8_t* tok_out;
+    uint32_t tok_region;
 };
 // P frames: pad the reference, shared integer motion search, then one wave per macroblock.
 // hp_planes: the four padded F / H / V / J planes (h264::launch_hpel) when the motion search refines
@@ -314,7 +331,10 @@ void launch_vp8_key(const h264::Geometry& g, const Vp8DeviceBuffers& b, const ui
 void launch_vp8_lf(const h264::Geometry& g, const Vp8DeviceBuffers& b, const uint8_t* src_y, const uint8_t* src_uv,
                    hipStream_t stream);
 // Records + the coded macroblocks' levels into the mapped host buffers (per-row compaction).
-void launch_vp8_gather(const h264::Geometry& g, const Vp8DeviceBuffers& b, hipStream_t stream);
+// levels false: the records only (b.lv_host may be null).
+void launch_vp8_gather(const h264::Geometry& g, const Vp8DeviceBuffers& b, hipStream_t stream, bool levels = true);
+// The token partitions boolean-coded into b.tok_out over the probabilities in its header, one workgroup each.
+void launch_vp8_tokens(const h264::Geometry& g, const Vp8DeviceBuffers& b, int log2_parts, hipStream_t stream);
 
 class GpuVp8Encoder final : public VideoEncoder {
    public:
@@ -342,16 +362,24 @@ class GpuVp8Encoder final : public VideoEncoder {
     h264::EncoderCommon& common() { return common_; }
     // records of the last collected frame (valid until that slot is submitted again)
     const Vp8Mb* last_mb_info() const { return last_mb_; }
+    // the token partitions are coded on the GPU (vp8_tokens resolved); frames and probes whose
+    // partitions outgrew their regions and were coded again on the host
+    bool gpu_tokens() const { return gpu_tokens_; }
+    long long token_fallbacks() const { return tok_fallbacks_.load(); }
 
    private:
     // Each frame slot has a writer thread: it waits for the slot's GPU work and writes the frame's
     // bitstream at once, so with several frames in flight their bitstreams are written concurrently;
     // collect() only waits for the writer of the oldest.  The writers' token partitions share one
-    // pool (pool_), sized to the machine, not one per slot.
+    // pool (pool_), sized to the machine, not one per slot.  With vp8_tokens 1 the GPU has coded the
+    // token partitions by then: the writer codes the first partition itself and puts the frame
+    // together, and the pool exists only once a partition overflowed its region (recode_on_host).
     struct Slot {
         Vp8DeviceBuffers buf{};
         Vp8States* st_host = nullptr;  // pinned: copied to buf.st at the start of the frame
         hipEvent_t start = nullptr, done = nullptr;
+        hipEvent_t redo = nullptr;     // vp8_tokens 1: the level gather of a frame coded again on the host
+        std::vector<uint8_t> upd;      // vp8_tokens 1: the frame's 1056 probability updates (first partition)
         bool key = false;
         int qp = 0, qindex = 0;
         bool segmented = false;
@@ -371,6 +399,9 @@ class GpuVp8Encoder final : public VideoEncoder {
         long long wt_n = 0;
     };
     std::unique_ptr<PartitionPool> pool_;
+    std::once_flag pool_once_;
+    bool gpu_tokens_ = false;
+    std::atomic<long long> tok_fallbacks_{0};
     void writer_loop(Slot& s);
     void alloc_slot(Slot& s);
     void free_slot(Slot& s);
@@ -378,6 +409,11 @@ class GpuVp8Encoder final : public VideoEncoder {
     int probe_bytes(const uint8_t* src_y, const uint8_t* src_uv, int qp);
     void check_slot(Slot& s);
     void write_slot(const Slot& s, std::vector<uint8_t>& out, bool probe = false);
+    // vp8_tokens 1: the frame from the GPU-coded partitions; false if one overflowed its region
+    bool write_slot_gpu(const Slot& s, std::vector<uint8_t>& out, bool probe);
+    void recode_on_host(Slot& s, std::vector<uint8_t>& out, bool probe);
+    FrameDesc frame_desc(const Slot& s) const;
+    PartitionPool& pool();
 
     h264::EncoderConfig cfg_;
     h264::EncoderCommon common_;

@@ -1,4 +1,5 @@
-// GpuVp8Encoder: HIP analysis (vp8_kernels.hip) + host boolean coding (vp8_bitstream.cpp).
+// GpuVp8Encoder: HIP analysis (vp8_kernels.hip) + host boolean coding (vp8_bitstream.cpp), or with
+// EncoderConfig::vp8_tokens 1 the token partitions boolean-coded on the GPU as well (vp8_tokens.hip).
 //
 // Per frame, on the caller's stream: one host->device copy of the frame states, the analysis
 // kernels (P: pad + shared motion search + k_vp8_inter; key: the k_vp8_key wavefront), then
@@ -6,6 +7,13 @@
 // collect() codes the first partition on the calling thread and the token partitions (one per
 // group of macroblock rows) on a small worker pool; with pipeline depth 2 that host work overlaps
 // the GPU analysis of the next frame.  Decisions and samples equal CpuVp8Encoder's (tests/test_gpu_vp8.py).
+//
+// vp8_tokens 1: prepare() plans the frame's coefficient probabilities (from the branch statistics of
+// the frame kStatsLag back, which the host holds by then) into the slot's mapped token block; k_vp8_tokens follows
+// the analysis kernels and leaves the coded partitions and their branch counts in mapped host memory,
+// k_vp8_gather sends the records only.  The slot's writer thread codes the first partition, puts the
+// frame together and sums the counts.  A partition that outgrew its region (vp8_tokens_cap) has the
+// frame coded again by the host path above, from the levels the slot still holds: the same bytes.
 #include <algorithm>
 #include <chrono>
 #include <memory>
@@ -21,6 +29,7 @@
 #include "h264_core.h"
 #include "h264_mb.h"
 #include "vp8_encoder.h"
+#include "vp8_tokens.h"
 
 namespace mx {
 namespace vp8 {
@@ -31,6 +40,15 @@ int pool_threads() {
     return (int)std::clamp(hc ? hc / 2 : 1u, 1u, 16u);
 }
 int log2_parts_for(int mb_h) { return mb_h >= 8 ? 3 : (mb_h >= 4 ? 2 : (mb_h >= 2 ? 1 : 0)); }
+// EncoderConfig::vp8_tokens resolved: -1 reads MXDESK_VP8_TOKENS (host | gpu; unset: host)
+bool gpu_tokens_from(int mode) {
+    if (mode >= 0) return mode == 1;
+    const char* e = std::getenv("MXDESK_VP8_TOKENS");
+    if (!e || !*e || std::string(e) == "host") return false;
+    if (std::string(e) == "gpu") return true;
+    throw std::invalid_argument("MXDESK_VP8_TOKENS must be host or gpu");
+}
+constexpr size_t kTokBytesAt = sizeof(Vp8TokenHeader) + sizeof(uint32_t) * 2 * kNumCoefProbs * kMaxTokenParts;
 }  // namespace
 
 void GpuVp8Encoder::alloc_slot(Slot& s) {
@@ -50,7 +68,17 @@ void GpuVp8Encoder::alloc_slot(Slot& s) {
     HIP_CHECK(hipHostMalloc(&b.err, sizeof(int), hipHostMallocMapped));
     *b.err = 0;
     HIP_CHECK(hipHostMalloc(&b.mb_host, sizeof(Vp8Mb) * (size_t)nmb, hipHostMallocMapped));
-    HIP_CHECK(hipHostMalloc(&b.lv_host, sizeof(int16_t) * kCoefPerMb * (size_t)nmb, hipHostMallocMapped));
+    if (gpu_tokens_) {  // the levels stay on the GPU (recode_on_host allocates lv_host if it ever runs)
+        const int nparts = 1 << log2_parts_, rows = (geom_.mb_h + nparts - 1) / nparts;
+        const size_t region = ((size_t)cfg_.vp8_tokens_cap * geom_.mb_w * rows + 3) & ~(size_t)3;
+        if (region > 0x7fffffffu) throw std::invalid_argument("vp8_tokens_cap too large");
+        b.tok_region = (uint32_t)region;
+        HIP_CHECK(hipHostMalloc(&b.tok_out, kTokBytesAt + region * nparts, hipHostMallocMapped));
+        std::memset(b.tok_out, 0, kTokBytesAt);
+        s.upd.assign(kNumCoefProbs, 0);
+    } else {
+        HIP_CHECK(hipHostMalloc(&b.lv_host, sizeof(int16_t) * kCoefPerMb * (size_t)nmb, hipHostMallocMapped));
+    }
     HIP_CHECK(hipMalloc(&b.me.mb, sizeof(h264::MbInfo) * (size_t)nmb));
     HIP_CHECK(hipMalloc(&b.icand, (size_t)nmb));
     HIP_CHECK(hipMalloc(&b.ilist, sizeof(int) * (size_t)(nmb + 1)));
@@ -65,9 +93,9 @@ void GpuVp8Encoder::free_slot(Slot& s) {
     Vp8DeviceBuffers& b = s.buf;
     for (void* p : {(void*)b.st, (void*)b.mb, (void*)b.lv, (void*)b.line, (void*)b.me.mb, (void*)b.lf_line, (void*)b.icand, (void*)b.ilist})
         if (p) (void)hipFree(p);
-    for (void* p : {(void*)b.err, (void*)b.mb_host, (void*)b.lv_host, (void*)s.st_host, (void*)b.lf_sse})
+    for (void* p : {(void*)b.err, (void*)b.mb_host, (void*)b.lv_host, (void*)s.st_host, (void*)b.lf_sse, (void*)b.tok_out})
         if (p) (void)hipHostFree(p);
-    for (hipEvent_t e : {s.start, s.done})
+    for (hipEvent_t e : {s.start, s.done, s.redo})
         if (e) (void)hipEventDestroy(e);
 }
 
@@ -90,6 +118,8 @@ GpuVp8Encoder::GpuVp8Encoder(const h264::EncoderConfig& cfg, hipStream_t stream)
     geom_.pitch = (geom_.coded_w + 255) & ~255;
     if (geom_.mb_w > 512) throw std::invalid_argument("vp8: picture too wide (k_vp8_gather ranks <= 512 MBs per row)");
     log2_parts_ = log2_parts_for(geom_.mb_h);
+    gpu_tokens_ = gpu_tokens_from(cfg.vp8_tokens);
+    if (gpu_tokens_ && cfg.vp8_tokens_cap < 1) throw std::invalid_argument("vp8_tokens_cap must be at least 1");
     const size_t ysz = (size_t)geom_.pitch * geom_.coded_h, uvsz = ysz / 2;
     for (int i = 0; i < 2; ++i) {
         HIP_CHECK(hipMalloc(&rec_y_[i], ysz));
@@ -111,8 +141,13 @@ GpuVp8Encoder::GpuVp8Encoder(const h264::EncoderConfig& cfg, hipStream_t stream)
     // one partition pool for all slot writers (a per-slot pool held up to 36 threads per session at
     // depth 4; a per-slot share of 8 threads cost 40 % of the single-session rate, 7,014 -> 4,413 fps:
     // profiles/r05_vp8/NOTES.md)
-    pool_ = std::make_unique<PartitionPool>(pool_threads());
+    if (!gpu_tokens_) (void)pool();
     for (int i = 0; i < depth_; ++i) slots_[i].writer = std::thread([this, i]() { writer_loop(slots_[i]); });
+}
+
+PartitionPool& GpuVp8Encoder::pool() {
+    std::call_once(pool_once_, [this]() { pool_ = std::make_unique<PartitionPool>(pool_threads()); });
+    return *pool_;
 }
 
 void GpuVp8Encoder::writer_loop(Slot& s) {
@@ -131,7 +166,10 @@ void GpuVp8Encoder::writer_loop(Slot& s) {
             } else {
                 const auto t0 = std::chrono::steady_clock::now();
                 s.au.clear();
-                write_slot(s, s.au);
+                if (!gpu_tokens_)
+                    write_slot(s, s.au);
+                else if (!write_slot_gpu(s, s.au, false))
+                    recode_on_host(s, s.au, false);
                 s.wt_us += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
                 ++s.wt_n;
                 const int nmb = geom_.mb_w * geom_.mb_h;
@@ -245,7 +283,8 @@ void GpuVp8Encoder::enqueue_body(bool key, const uint8_t* src_y, const uint8_t* 
         launch_vp8_inter(geom_, s.buf, planes, hp_pitch_, cfg_.subpel != 0, src_y, src_uv, stream_, cfg_.vp8_intra != 0);
     }
     if (s.lf_on) launch_vp8_lf(geom_, s.buf, src_y, src_uv, stream_);
-    launch_vp8_gather(geom_, s.buf, stream_);
+    if (gpu_tokens_) launch_vp8_tokens(geom_, s.buf, log2_parts_, stream_);
+    launch_vp8_gather(geom_, s.buf, stream_, !gpu_tokens_);
     HIP_CHECK(hipGetLastError());
 }
 
@@ -257,15 +296,65 @@ void GpuVp8Encoder::check_slot(Slot& s) {
     }
 }
 
-void GpuVp8Encoder::write_slot(const Slot& s, std::vector<uint8_t>& out, bool probe) {
-    const Vp8Mb* mbs = s.buf.mb_host;
-    const int16_t* lv = s.buf.lv_host;
+FrameDesc GpuVp8Encoder::frame_desc(const Slot& s) const {
     FrameDesc fd{s.key, cfg_.width, cfg_.height, geom_.mb_w, geom_.mb_h, s.qindex, log2_parts_};
     fd.segmented = s.segmented;
     for (int k = 0; k < kNumSegs; ++k) {
         fd.seg_qindex[k] = s.seg_qindex[k];
         fd.lf_level[k] = s.lf_level[k];
     }
+    return fd;
+}
+
+bool GpuVp8Encoder::write_slot_gpu(const Slot& s, std::vector<uint8_t>& out, bool probe) {
+    const Vp8TokenHeader* h = reinterpret_cast<const Vp8TokenHeader*>(s.buf.tok_out);
+    const int nparts = 1 << log2_parts_;
+    const uint8_t* ptr[kMaxTokenParts];
+    uint32_t len[kMaxTokenParts];
+    for (int p = 0; p < nparts; ++p) {
+        if (h->overflow[p] || h->len[p] > s.buf.tok_region) return false;
+        ptr[p] = s.buf.tok_out + kTokBytesAt + (size_t)p * s.buf.tok_region;
+        len[p] = h->len[p];
+    }
+    const FrameDesc fd = frame_desc(s);
+    std::vector<uint8_t> p1;
+    write_first_partition(fd, s.buf.mb_host, s.upd.data(), p1);
+    assemble_frame(fd, p1, ptr, len, out);
+    if (!probe) {  // this frame's branch statistics, as write_frame leaves them
+        TokenStats& ts = tok_stats_[s.key ? 1 : 0][s.fidx % kStatsLag];
+        const uint32_t* n = reinterpret_cast<const uint32_t*>(s.buf.tok_out + sizeof(Vp8TokenHeader));
+        ts.n.assign(kNumCoefProbs, std::array<uint32_t, 2>{0u, 0u});
+        for (int p = 0; p < nparts; ++p)
+            for (int k = 0; k < kNumCoefProbs; ++k) {
+                ts.n[(size_t)k][0] += n[((size_t)p * kNumCoefProbs + k) * 2];
+                ts.n[(size_t)k][1] += n[((size_t)p * kNumCoefProbs + k) * 2 + 1];
+            }
+        ts.valid = true;
+        ts.us_first = ts.us_tokens = 0;
+    }
+    return true;
+}
+
+void GpuVp8Encoder::recode_on_host(Slot& s, std::vector<uint8_t>& out, bool probe) {
+    // a partition outgrew its region: the levels are still in the slot's device buffer, so the
+    // level-carrying gather and the host writer code the frame as with vp8_tokens 0
+    Vp8DeviceBuffers& b = s.buf;
+    ++tok_fallbacks_;
+    if (!b.lv_host)
+        HIP_CHECK(hipHostMalloc(&b.lv_host, sizeof(int16_t) * kCoefPerMb * (size_t)geom_.mb_w * geom_.mb_h, hipHostMallocMapped));
+    if (!s.redo) HIP_CHECK(hipEventCreate(&s.redo));
+    launch_vp8_gather(geom_, b, stream_, true);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipEventRecord(s.redo, stream_));
+    HIP_CHECK(hipEventSynchronize(s.redo));
+    out.clear();
+    write_slot(s, out, probe);
+}
+
+void GpuVp8Encoder::write_slot(const Slot& s, std::vector<uint8_t>& out, bool probe) {
+    const Vp8Mb* mbs = s.buf.mb_host;
+    const int16_t* lv = s.buf.lv_host;
+    const FrameDesc fd = frame_desc(s);
     // k_vp8_gather sent only the blocks with a non-zero level (16 levels each, from block `slot`):
     // expanded into the 25-block layout the token writer reads, one macroblock at a time per thread
     auto levels = [&](int i) -> const int16_t* {
@@ -283,7 +372,7 @@ void GpuVp8Encoder::write_slot(const Slot& s, std::vector<uint8_t>& out, bool pr
         return full;
     };
     write_frame(fd, mbs, levels, out,
-                [&](int n, const std::function<void(int)>& fn) { pool_->run(n, fn); },
+                [&](int n, const std::function<void(int)>& fn) { pool().run(n, fn); },
                 probe ? nullptr : &tok_stats_[s.key ? 1 : 0][s.fidx % kStatsLag]);
 }
 
@@ -295,11 +384,16 @@ int GpuVp8Encoder::probe_bytes(const uint8_t* src_y, const uint8_t* src_uv, int 
     Slot& s = slots_[0];
     s.key = true;
     fill_state(s, true, qp, cur_ ^ 1, cur_);
+    if (gpu_tokens_)  // a probe: the default probabilities
+        plan_token_probs(nullptr, s.upd.data(), reinterpret_cast<Vp8TokenHeader*>(s.buf.tok_out)->probs);
     enqueue_body(true, src_y, src_uv);
     HIP_CHECK(hipStreamSynchronize(stream_));
     check_slot(s);
     std::vector<uint8_t> tmp;
-    write_slot(s, tmp, true);
+    if (!gpu_tokens_)
+        write_slot(s, tmp, true);
+    else if (!write_slot_gpu(s, tmp, true))
+        recode_on_host(s, tmp, true);
     return (int)tmp.size();
 }
 
@@ -317,6 +411,10 @@ bool GpuVp8Encoder::prepare(bool force_idr) {
     const int ref = cur_;
     cur_ ^= 1;
     fill_state(s, s.key, s.qp, ref, cur_);
+    // frame n - kStatsLag of this type has been collected: its statistics plan this frame's probabilities
+    if (gpu_tokens_)
+        plan_token_probs(&tok_stats_[s.key ? 1 : 0][s.fidx % kStatsLag], s.upd.data(),
+                         reinterpret_cast<Vp8TokenHeader*>(s.buf.tok_out)->probs);
     lf_levels(lf_.decide(s.fidx, s.key), s.segmented, s.qindex, s.seg_qindex, lf_num_, s.lf_level);
     for (int k = 0; k < kNumSegs; ++k) {
         s.st_host->v.lf_level[k] = s.lf_level[k];

@@ -4,7 +4,9 @@
 //   P frame:   k_vp8_pad (or the H.264 k_hpel planes with subpel) -> k_me_full (shared with
 //              H.264) -> k_vp8_inter [-> k_vp8_lf] -> k_vp8_gather
 //   key frame: k_vp8_key [-> k_vp8_lf] -> k_vp8_gather
-//   (k_vp8_lf: the loop filter, when the frame's levels are not all zero)
+//   (k_vp8_lf: the loop filter, when the frame's levels are not all zero; with vp8_tokens 1
+//   k_vp8_tokens, vp8_tokens.hip, codes the token partitions before k_vp8_gather, which then sends
+//   the records only)
 //
 // One 64-lane wave codes one macroblock: lanes 0..15 own the luma 4x4 blocks, 16..23 the chroma
 // blocks, lane 24 the second-order Y2 block -- the block index of a lane is its token block index,
@@ -1460,6 +1462,7 @@ __global__ __launch_bounds__(256) void k_vp8_gather(h264::Geometry g, const Vp8M
             bmap[wave][k] = (uint16_t)((i << 5) | bb);
         }
     }
+    if (lv_host == nullptr) return;  // records only (vp8_tokens 1: the levels are coded on the GPU)
     wave_lds_sync();
     // two uint4 per block, spread over the lanes: many copies in flight per wave
     const uint4* __restrict__ src = reinterpret_cast<const uint4*>(lv + (size_t)base * kCoefPerMb);
@@ -1509,8 +1512,9 @@ void launch_vp8_lf(const h264::Geometry& g, const Vp8DeviceBuffers& b, const uin
     hipLaunchKernelGGL(k_vp8_lf_sse, dim3(g.mb_h), dim3(256), 0, stream, g, b.st, src_y, src_uv, b.lf_sse);
 }
 
-void launch_vp8_gather(const h264::Geometry& g, const Vp8DeviceBuffers& b, hipStream_t stream) {
-    hipLaunchKernelGGL(k_vp8_gather, dim3(g.mb_h), dim3(256), 0, stream, g, b.mb, b.lv, b.mb_host, b.lv_host);
+void launch_vp8_gather(const h264::Geometry& g, const Vp8DeviceBuffers& b, hipStream_t stream, bool levels) {
+    hipLaunchKernelGGL(k_vp8_gather, dim3(g.mb_h), dim3(256), 0, stream, g, b.mb, b.lv, b.mb_host,
+                       levels ? b.lv_host : nullptr);
 }
 
 }  // namespace vp8

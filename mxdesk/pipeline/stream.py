@@ -209,6 +209,8 @@ def apply_encoder_args(enc, a: dict) -> None:
     enc.subpel = 1 if a["subpel"] else 0
     if "hevc_intra_split" in a:  # HEVC I pictures: transform-tree depth (EncoderConfig::hevc_intra_split)
         enc.hevc_intra_split = a["hevc_intra_split"]
+    if "vp8_tokens" in a:  # VP8 token partitions coded on the host or the GPU (EncoderConfig::vp8_tokens)
+        enc.vp8_tokens = 1 if a["vp8_tokens"] == "gpu" else 0
 
 
 class StreamPipeline:
@@ -218,7 +220,7 @@ class StreamPipeline:
                  capture: Any = None, metrics: SessionMetrics | None = None, queue_frames: int | None = None,
                  stall_s: float = 2.0, paced: bool = True, codec: str = "h264",
                  idr_min_interval_s: float | None = None, scroll_range: int = 0, partitions: int = 1,
-                 hevc_intra_split: int = 1):
+                 hevc_intra_split: int = 1, vp8_tokens: str = "host"):
         if codec not in CODEC_IDS:
             raise ValueError(f"unknown codec {codec!r} (h264 | hevc | vp8)")
         self.codec = codec
@@ -238,7 +240,7 @@ class StreamPipeline:
         self.bitrate_kbps = bitrate_kbps  # configured CBR target (congestion control upper bound)
         self._enc_args = dict(bitrate_kbps=bitrate_kbps, keyint=keyint, search_range=search_range, subpel=subpel,
                               noise=noise, scroll_range=scroll_range, partitions=partitions,
-                              hevc_intra_split=hevc_intra_split)
+                              hevc_intra_split=hevc_intra_split, vp8_tokens=vp8_tokens)
         self.last_scroll = (0, 0)  # scroll hint of the last P picture (H.264 with scroll_range; /status)
         self._subs: list[_Subscriber] = []
         self._lock = threading.Lock()
@@ -552,11 +554,20 @@ class StreamPipeline:
     def healthy(self) -> bool:
         return self._thread is not None and (time.monotonic() - self.last_frame_t) < self.stall_s
 
+    def _vp8_tokens_status(self) -> dict | None:
+        """VP8: who codes the token partitions (as the encoder resolved it) and the frames that a GPU
+        coder's overflow sent through the host writer again."""
+        if self.codec != "vp8":
+            return None
+        t = self._sess.vp8_tokens if self._sess is not None else None
+        return {"coder": t[0], "fallbacks": int(t[1])} if t else {"coder": "host", "fallbacks": 0}
+
     def status(self) -> dict:
         return {"backend": self.backend, "device": self.device, "width": self.out_w, "height": self.out_h,
                 "fps": self.fps, "frames": self.frames_out, "clients": self.subscribers, "restarts": self.restarts,
                 "last_error": self.last_error, "resizes": self.resizes, "keyframes": self.keyframes.snapshot(),
                 "frames_idle": self.frames_idle, "scroll_hint": list(self.last_scroll),
+                "vp8_tokens": self._vp8_tokens_status(),
                 **self.metrics.summary()}
 
 

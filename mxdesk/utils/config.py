@@ -158,6 +158,8 @@ SCHEMA: list[Var] = [
     Var("hevc_intra_split", ["MXDESK_HEVC_INTRA_SPLIT"], 1, int,
         "HEVC I pictures, transform tree of a 16x16 unit: 0 = one 16x16 luma TU, 1 = may split into four 8x8 luma TUs, "
         "2 = and those into four 4x4 luma TUs (DST-VII)"),
+    Var("vp8_tokens", ["MXDESK_VP8_TOKENS"], "host", str,
+        "VP8 token partitions boolean-coded by: host (writer threads) | gpu (k_vp8_tokens; same stream)"),
     Var("subpel", ["MXDESK_SUBPEL"], True, bool, "quarter-pel motion refinement"),
     Var("noise", ["MXDESK_NOISE"], True, bool, "synthetic desktop: animated-noise panel"),
     Var("wall", ["MXDESK_WALL"], "", str, "tiled wall layout, e.g. '2x2' (one tile per GPU)"),
@@ -272,6 +274,8 @@ class Config:
             raise ValueError("MXDESK_H264_PARTITIONS must be 0, 1 or 2")
         if v["hevc_intra_split"] not in (0, 1, 2):
             raise ValueError("MXDESK_HEVC_INTRA_SPLIT must be 0, 1 or 2")
+        if v["vp8_tokens"] not in ("host", "gpu"):
+            raise ValueError("MXDESK_VP8_TOKENS must be host or gpu")
         if v["source"] not in ("auto", "synthetic", "x11"):
             raise ValueError("MXDESK_SOURCE must be auto, synthetic or x11")
         self.encoder_backend  # noqa: B018  (raises on unknown encoders)
