@@ -112,6 +112,11 @@ struct EncoderConfig {
     // component), max_transform_hierarchy_depth_intra 2, decided per node open-loop as well (hevc_core.h
     // intra_tu4_wins).  0 and 1 code the streams they always coded.
     int hevc_intra_split = 1;
+    // HEVC P pictures: a 16x16 unit may be coded intra (one 16x16 luma TU, DM chroma) from the unfiltered
+    // inter reconstruction around it where that beats its motion-compensated prediction (hevc_core.h
+    // intra_p_gain); the units chosen in one picture never touch each other (intra_p_selected).  0: every
+    // unit of a P picture is inter, the streams are what they always were.  (intra_in_p above is H.264's.)
+    int hevc_intra_in_p = 0;
     int hevc_slice_cost = 1536;  // HEVC without WPP: P-picture slice work target (hevc_core.h cu_cost units)
     // HEVC wavefront parallel processing (entropy_coding_sync_enabled_flag): P pictures in slices of
     // hevc_wpp_rows CTU rows, every CTU row its own CABAC substream (one GPU wave each) that starts

@@ -2477,12 +2477,16 @@ MXHD void decide_inter(CuInfo& c, const PuNb& nb) {
 // picture, in the slice and earlier in decoding order (z order inside a CTB: e.g. the A0 of a CTB's
 // first unit lies in the left CTB and is available, the B0 of its last unit is not).  mv: per unit
 // quarter-pel motion, (x, y) at mv[u * stride], mv[u * stride + 1].
-MXHD PuNb pu_neighbours(const int16_t* mv, int stride, int x, int y, int n, int mb_w, int mb_h, int first_ctb) {
+// intra (P pictures with intra units, EncoderConfig::hevc_intra_in_p; else nullptr): per unit,
+// nonzero = coded intra -- such a neighbour carries no motion and is not a candidate.
+MXHD PuNb pu_neighbours(const int16_t* mv, int stride, int x, int y, int n, int mb_w, int mb_h, int first_ctb,
+                        const uint8_t* intra = nullptr) {
     const int cw = ctb_cols(mb_w), cur = cpos_of(x, y, cw);
     auto at = [&](int xn, int yn) {
         MvCand c{false, 0, 0};
         if (xn < 0 || yn < 0 || xn >= mb_w || yn >= mb_h) return c;
         if (ctb_of(xn, yn, cw) < first_ctb || cpos_of(xn, yn, cw) >= cur) return c;
+        if (intra && intra[yn * mb_w + xn]) return c;
         c.avail = true;
         c.x = mv[(size_t)(yn * mb_w + xn) * stride];
         c.y = mv[(size_t)(yn * mb_w + xn) * stride + 1];
@@ -2501,21 +2505,27 @@ MXHD PuNb pu_neighbours(const int16_t* mv, int stride, int x, int y, int n, int 
 // picture) against the slice's neighbours, then the coding tree: the four units become one CU32
 // when all lie inside the picture with one vector and one QP, and the CU32's merge list holds the
 // vector (one skip / merge_idx instead of four) or its first unit needs AMVP anyway (one mvd).
-// Shared by both encoders (k_hevc_decide: one thread per CTB).
+// Shared by both encoders (k_hevc_decide: one thread per CTB).  intra: as pu_neighbours -- an intra
+// unit (type kCuIntra already) stays as it is, a CU16, and its CTB never becomes a CU32.
 MXHD void decide_ctb(CuInfo* u, const bool* in, const int16_t* mv, int stride, int x0, int y0, int mb_w, int mb_h,
-                     int first_ctb) {
+                     int first_ctb, const uint8_t* intra = nullptr) {
+    bool has_intra = false;
     for (int z = 0; z < 4; ++z) {
         if (!in[z]) continue;
-        decide_inter(u[z], pu_neighbours(mv, stride, x0 + (z & 1), y0 + (z >> 1), 1, mb_w, mb_h, first_ctb));
+        if (intra && u[z].type == kCuIntra) {
+            has_intra = true;
+            continue;
+        }
+        decide_inter(u[z], pu_neighbours(mv, stride, x0 + (z & 1), y0 + (z >> 1), 1, mb_w, mb_h, first_ctb, intra));
         u[z].ct = 1;
     }
-    if (!(in[0] && in[1] && in[2] && in[3])) return;
+    if (has_intra || !(in[0] && in[1] && in[2] && in[3])) return;
     uint32_t any = 0;
     for (int z = 0; z < 4; ++z) {
         if (u[z].mvx != u[0].mvx || u[z].mvy != u[0].mvy || u[z].qp != u[0].qp) return;
         any |= u[z].cbf;
     }
-    const PuNb nb = pu_neighbours(mv, stride, x0, y0, 2, mb_w, mb_h, first_ctb);
+    const PuNb nb = pu_neighbours(mv, stride, x0, y0, 2, mb_w, mb_h, first_ctb, intra);
     const int k = merge_index_of(nb, u[0].mvx, u[0].mvy);
     if (k < 0 && u[0].type != kCuAmvp) return;
     CuInfo h = u[0];
@@ -2528,6 +2538,65 @@ MXHD void decide_ctb(CuInfo* u, const bool* in, const int16_t* mv, int stride, i
         u[z].mvdy = h.mvdy;
         u[z].ct = 0;
     }
+}
+
+// ---------------------------------------------------------------- intra units in P pictures
+// EncoderConfig::hevc_intra_in_p.  After the inter pass and the slice layout every unit is scored
+// as a 16x16 intra unit predicted from the unfiltered inter reconstruction around it, and a unit
+// whose gain is positive and a strict maximum among its eight neighbours (ties to the lower raster
+// index) is coded intra.  The selected units form an independent set: none references another, so
+// the prediction that was scored is the prediction that is coded, and all of them run in parallel.
+// A dense cluster gets about a quarter of its units per picture; the rest follow in later pictures.
+// All costs are luma 4x4-Hadamard SATDs (unnormalised, the scale of intra_decide_mode); lambda is
+// h264::lambda_sad of the unit's QP.
+//
+// Units worth scoring: the inter prediction leaves more than 4 per sample or 64 lambda (the
+// quantiser's dead zone swallows smaller residuals whatever predicts them).
+MXHD bool intra_p_candidate(uint32_t inter_satd, int lambda) {
+    const uint32_t floor = 64u * (uint32_t)lambda;
+    return inter_satd > (floor > 256u * 4u ? floor : 256u * 4u);
+}
+// Reference availability (6.4.1) of unit (x, y) in the slice that starts at CTB first_ctb, as the bits
+// of split_tu_avl: 0 below-left, 1 left, 2 corner, 3 top, 4 top-right -- each a whole unit, available
+// when inside the picture, not before the slice and earlier in z order (the rule of pu_neighbours).
+MXHD int intra_p_avl(int x, int y, int mb_w, int mb_h, int first_ctb) {
+    const int cw = ctb_cols(mb_w), cur = cpos_of(x, y, cw);
+    auto at = [&](int xn, int yn) {
+        if (xn < 0 || yn < 0 || xn >= mb_w || yn >= mb_h) return 0;
+        return (ctb_of(xn, yn, cw) >= first_ctb && cpos_of(xn, yn, cw) < cur) ? 1 : 0;
+    };
+    return at(x - 1, y + 1) | (at(x - 1, y) << 1) | (at(x - 1, y - 1) << 2) | (at(x, y - 1) << 3) | (at(x + 1, y - 1) << 4);
+}
+// Bits the unit's motion costs, estimated before k_hevc_decide: the mvd against the left unit's
+// motion-search vector (zero at the left picture edge) plus merge_flag / mvp flag.
+MXHD int intra_p_motion_bits(const int16_t* mv, int stride, int x, int y, int mb_w) {
+    const size_t u = (size_t)(y * mb_w + x) * stride;
+    const int px = x > 0 ? mv[u - stride] : 0, py = x > 0 ? mv[u - stride + 1] : 0;
+    return mvd_cost_bits(mv[u] - px) + mvd_cost_bits(mv[u + 1] - py) + 2;
+}
+// pred_mode_flag, part_mode and intra_chroma_pred_mode next to the luma mode's bins
+constexpr int kIntraPHeadBits = 3;
+// Gain of coding the unit intra: inter cost + lambda * motion bits - intra cost - lambda * head
+// bits, where the intra cost carries 1/8 on top of its SATD (at equal SATD the intra quantiser's
+// rounding codes more levels than the inter one's).  The unit keeps its class QP either way, so
+// content that neither prediction serves needs no rule of its own.  0: stays inter.
+MXHD int intra_p_gain(uint32_t inter_satd, int motion_bits, uint32_t intra_satd, int mode_bits, int lambda) {
+    const int g = (int)inter_satd + lambda * motion_bits - (int)(intra_satd + (intra_satd >> 3)) -
+                  lambda * (mode_bits + kIntraPHeadBits);
+    return g > 0 ? g : 0;
+}
+MXHD bool intra_p_selected(const int32_t* gain, int mb_w, int mb_h, int x, int y) {
+    const int i = y * mb_w + x;
+    const int32_t g = gain[i];
+    if (g <= 0) return false;
+    for (int dy = -1; dy <= 1; ++dy)
+        for (int dx = -1; dx <= 1; ++dx) {
+            const int xn = x + dx, yn = y + dy;
+            if ((dx | dy) == 0 || xn < 0 || yn < 0 || xn >= mb_w || yn >= mb_h) continue;
+            const int j = yn * mb_w + xn;
+            if (gain[j] > g || (gain[j] == g && j < i)) return false;
+        }
+    return true;
 }
 
 // ---------------------------------------------------------------- deblocking (8.7.2)

@@ -395,6 +395,8 @@ CpuHevcEncoder::CpuHevcEncoder(const EncoderConfig& cfg) : cfg_(cfg.with_aq_defa
     coef_.resize(n * kCoefPerCu);
     qp_pred_.assign(n, 0);
     qpy_.assign(n, 0);
+    inter_satd_.assign(n, 0);
+    intra_sel_.assign(n, 0);
     bl_safe_ = bl_safe_modes(4, 0) & bl_safe_modes(3, 1);  // the 16x16 luma mode and its DM chroma
     bl_safe_split_ = bl_safe_split();
 }
@@ -495,6 +497,33 @@ void block_refs(const uint8_t* p, int pitch, int step, int x, int y, int N, int 
     const int corner = (avl & 4) ? px(x - 1, y - 1) : 0;
     intra_refs(N, (avl & 2) != 0, (avl & 1) != 0, (avl & 8) != 0, (avl & 16) != 0, (avl & 4) != 0, lp, bp, tp, tr,
                corner, L, T);
+}
+
+// One unsplit intra unit at luma (x0, y0): the 16x16 luma TU and the two DM 8x8 chroma TUs predicted in
+// `mode` from the reconstruction (ry / ruv, pitch cw) with reference availability avl (split_tu_avl
+// bits), coded at qp / qpc; levels to co, the reconstruction written back.
+void code_intra16(const uint8_t* sy, const uint8_t* suv, int pitch, uint8_t* ry, uint8_t* ruv, int cw, int x0, int y0,
+                  int avl, int mode, int qp, int qpc, int16_t* co) {
+    int L[33], T[33], pred[256], res[256], rr[256];
+    block_refs(ry, cw, 1, x0, y0, 16, avl, L, T);
+    intra_predict(mode, 4, 0, L, T, pred);
+    for (int r = 0; r < 16; ++r)
+        for (int q = 0; q < 16; ++q) res[r * 16 + q] = sy[(size_t)(y0 + r) * pitch + x0 + q] - pred[r * 16 + q];
+    tu_encode(4, res, qp, true, co, rr);
+    for (int r = 0; r < 16; ++r)
+        for (int q = 0; q < 16; ++q) ry[(size_t)(y0 + r) * cw + x0 + q] = (uint8_t)clip255(pred[r * 16 + q] + rr[r * 16 + q]);
+    const int xc = x0 / 2, yc = y0 / 2;
+    for (int comp = 0; comp < 2; ++comp) {
+        int Lc[17], Tc[17], pc[64], rc[64], rrc[64];
+        block_refs(ruv + comp, cw, 2, xc, yc, 8, avl, Lc, Tc);
+        intra_predict(mode, 3, 1 + comp, Lc, Tc, pc);
+        for (int r = 0; r < 8; ++r)
+            for (int q = 0; q < 8; ++q) rc[r * 8 + q] = suv[(size_t)(yc + r) * pitch + 2 * (xc + q) + comp] - pc[r * 8 + q];
+        tu_encode(3, rc, qpc, true, co + 256 + 64 * comp, rrc);
+        for (int r = 0; r < 8; ++r)
+            for (int q = 0; q < 8; ++q)
+                ruv[(size_t)(yc + r) * cw + 2 * (xc + q) + comp] = (uint8_t)clip255(pc[r * 8 + q] + rrc[r * 8 + q]);
+    }
 }
 }  // namespace
 
@@ -656,42 +685,8 @@ void CpuHevcEncoder::analyse_intra(const uint8_t* sy, const uint8_t* suv, int pi
                 mv_[2 * i] = mv_[2 * i + 1] = 0;
                 continue;
             }
-            uint8_t lp[16], tp[16], tr[16];
-            for (int k = 0; k < 16; ++k) {
-                lp[k] = al ? ry[(y0 + k) * cw_ + x0 - 1] : 0;
-                tp[k] = at ? ry[(y0 - 1) * cw_ + x0 + k] : 0;
-                tr[k] = atr ? ry[(y0 - 1) * cw_ + x0 + 16 + k] : 0;
-            }
-            const int corner = ac ? ry[(y0 - 1) * cw_ + x0 - 1] : 0;
-            int L[33], T[33];
-            intra_refs(16, al, false, at, atr, ac, lp, lp, tp, tr, corner, L, T);
-            int pred[256];
-            intra_predict(best, 4, 0, L, T, pred);
-            int res[256], rr[256];
-            for (int r = 0; r < 16; ++r)
-                for (int q = 0; q < 16; ++q) res[r * 16 + q] = sy[(y0 + r) * pitch + x0 + q] - pred[r * 16 + q];
-            tu_encode(4, res, qp, true, co, rr);
-            for (int r = 0; r < 16; ++r)
-                for (int q = 0; q < 16; ++q) ry[(y0 + r) * cw_ + x0 + q] = (uint8_t)clip255(pred[r * 16 + q] + rr[r * 16 + q]);
-            for (int comp = 0; comp < 2; ++comp) {
-                const int xc = x0 / 2, yc = y0 / 2;
-                uint8_t lc[8], tc[8], trc[8];
-                for (int k = 0; k < 8; ++k) {
-                    lc[k] = al ? ruv[(yc + k) * cw_ + 2 * (xc - 1) + comp] : 0;
-                    tc[k] = at ? ruv[(yc - 1) * cw_ + 2 * (xc + k) + comp] : 0;
-                    trc[k] = atr ? ruv[(yc - 1) * cw_ + 2 * (xc + 8 + k) + comp] : 0;
-                }
-                const int cc = ac ? ruv[(yc - 1) * cw_ + 2 * (xc - 1) + comp] : 0;
-                int Lc[17], Tc[17], pc[64], rc[64], rrc[64];
-                intra_refs(8, al, false, at, atr, ac, lc, lc, tc, trc, cc, Lc, Tc);
-                intra_predict(best, 3, 1 + comp, Lc, Tc, pc);
-                for (int r = 0; r < 8; ++r)
-                    for (int q = 0; q < 8; ++q) rc[r * 8 + q] = suv[(yc + r) * pitch + 2 * (xc + q) + comp] - pc[r * 8 + q];
-                tu_encode(3, rc, qpc, true, co + 256 + 64 * comp, rrc);
-                for (int r = 0; r < 8; ++r)
-                    for (int q = 0; q < 8; ++q)
-                        ruv[(yc + r) * cw_ + 2 * (xc + q) + comp] = (uint8_t)clip255(pc[r * 8 + q] + rrc[r * 8 + q]);
-            }
+            code_intra16(sy, suv, pitch, ry, ruv, cw_, x0, y0, (al ? 2 : 0) | (ac ? 4 : 0) | (at ? 8 : 0) | (atr ? 16 : 0),
+                         best, qp, qpc, co);
             summarise(c, co);
             mv_[2 * i] = mv_[2 * i + 1] = 0;
         }
@@ -729,6 +724,7 @@ void CpuHevcEncoder::analyse_inter(const uint8_t* sy, const uint8_t* suv, int pi
                     res[r * 16 + q] = sy[(y0 + r) * pitch + x0 + q] - p;
                     lsad += (uint32_t)std::abs(res[r * 16 + q]);
                 }
+            if (cfg_.hevc_intra_in_p) inter_satd_[(size_t)i] = (uint32_t)satd16(sy, pitch, x0, y0, pred);
             // temporal class (aq 3): the source's change against the previous source, displaced by
             // the integer part of the vector
             uint32_t tsad = 0;
@@ -819,6 +815,8 @@ void CpuHevcEncoder::analyse_inter(const uint8_t* sy, const uint8_t* suv, int pi
     // slice's neighbours and the coding tree (CU32 or four CU16)
     slices_ = common_.plan_p_slices(cu_);
     const int cw = common_.c32_w(), nctb = common_.num_ctbs();
+    if (cfg_.hevc_intra_in_p) intra_in_p(sy, suv, pitch);
+    const uint8_t* intra = cfg_.hevc_intra_in_p ? intra_sel_.data() : nullptr;
     for (size_t s = 0; s < slices_.size(); ++s) {
         const int first = slices_[s], end = s + 1 < slices_.size() ? slices_[s + 1] : nctb;
         for (int c = first; c < end; ++c) {
@@ -830,12 +828,59 @@ void CpuHevcEncoder::analyse_inter(const uint8_t* sy, const uint8_t* suv, int pi
                 in[z] = x < W && y < H;
                 if (in[z]) u[z] = cu_[(size_t)(y * W + x)];
             }
-            decide_ctb(u, in, mv_.data(), 2, x0, y0, W, H, first);
+            decide_ctb(u, in, mv_.data(), 2, x0, y0, W, H, first, intra);
             for (int z = 0; z < 4; ++z)
                 if (in[z]) cu_[(size_t)((y0 + (z >> 1)) * W + x0 + (z & 1))] = u[z];
         }
     }
     (void)sr;
+}
+
+void CpuHevcEncoder::intra_in_p(const uint8_t* sy, const uint8_t* suv, int pitch) {
+    uint8_t* ry = rec_y_[cur_].data();
+    uint8_t* ruv = rec_uv_[cur_].data();
+    const int W = common_.ctb_w(), H = common_.ctb_h(), cw = common_.c32_w(), nctb = common_.num_ctbs();
+    std::vector<int> first_of((size_t)nctb);  // first CTB of every CTB's slice
+    for (size_t s = 0; s < slices_.size(); ++s)
+        for (int c = slices_[s]; c < (s + 1 < slices_.size() ? slices_[s + 1] : nctb); ++c) first_of[(size_t)c] = slices_[s];
+    // every unit's best intra mode against the inter reconstruction around it, and its gain
+    std::vector<int32_t> gain((size_t)W * H, 0);
+    std::vector<uint8_t> mode((size_t)W * H, 1), avl((size_t)W * H, 0);
+    for (int y = 0; y < H; ++y)
+        for (int x = 0; x < W; ++x) {
+            const int i = y * W + x, x0 = x * 16, y0 = y * 16;
+            const int lambda = h264::lambda_sad(cu_[(size_t)i].qp);
+            avl[(size_t)i] = (uint8_t)intra_p_avl(x, y, W, H, first_of[(size_t)ctb_of(x, y, cw)]);
+            if (!intra_p_candidate(inter_satd_[(size_t)i], lambda)) continue;
+            int L[33], T[33], pred[256];
+            block_refs(ry, cw_, 1, x0, y0, 16, avl[(size_t)i], L, T);
+            auto cost = [&](int m) {
+                intra_predict(m, 4, 0, L, T, pred);
+                return satd16(sy, pitch, x0, y0, pred) + lambda * intra_mode_bits(m, 1, 1);  // the neighbours are inter: MPM of DC
+            };
+            const int best = intra_mode_search(cost), bits = intra_mode_bits(best, 1, 1);
+            mode[(size_t)i] = (uint8_t)best;
+            gain[(size_t)i] = intra_p_gain(inter_satd_[(size_t)i], intra_p_motion_bits(mv_.data(), 2, x, y, W),
+                                           (uint32_t)(cost(best) - lambda * bits), bits, lambda);
+        }
+    // the selected units touch no other selected unit: each is coded from the references it was scored with
+    for (int y = 0; y < H; ++y)
+        for (int x = 0; x < W; ++x) {
+            const int i = y * W + x;
+            intra_sel_[(size_t)i] = intra_p_selected(gain.data(), W, H, x, y) ? 1 : 0;
+            if (!intra_sel_[(size_t)i]) continue;
+            CuInfo& c = cu_[(size_t)i];
+            const int qp = c.qp;  // the class QP of the inter pass
+            std::memset(&c, 0, sizeof c);
+            c.type = kCuIntra;
+            c.intra_mode = mode[(size_t)i];
+            c.qp = (uint8_t)qp;
+            c.ct = 1;
+            int16_t* co = coef_.data() + (size_t)i * kCoefPerCu;
+            code_intra16(sy, suv, pitch, ry, ruv, cw_, x * 16, y * 16, avl[(size_t)i], c.intra_mode, qp,
+                         chroma_qp(qp, cfg_.chroma_qp_offset), co);
+            summarise(c, co);
+        }
 }
 
 const std::vector<uint8_t>& CpuHevcEncoder::encode(const uint8_t* y, const uint8_t* uv, int pitch, bool force_idr) {

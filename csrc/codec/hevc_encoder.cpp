@@ -40,6 +40,12 @@ void GpuHevcEncoder::alloc_slot(FrameSlot& sl) {
     HIP_CHECK(hipMalloc(&b.qp_pred, ncu));
     HIP_CHECK(hipMalloc(&b.imode, ncu));
     HIP_CHECK(hipMalloc(&b.itu4, ncu));
+    if (cfg_.hevc_intra_in_p) {
+        HIP_CHECK(hipMalloc(&b.isatd, sizeof(uint32_t) * ncu));
+        HIP_CHECK(hipMalloc(&b.igain, sizeof(int32_t) * ncu));
+        HIP_CHECK(hipMalloc(&b.ipmode, ncu));
+        HIP_CHECK(hipMalloc(&b.isel, ncu));
+    }
     // arrays scanned in 4096-entry tiles of 16-byte loads (per CTB costs, per coding position token
     // counts): padded with zeros to a whole tile
     auto pad = [](size_t n) { return (n + kScanTilePad - 1) / kScanTilePad * kScanTilePad + 4; };
@@ -81,7 +87,8 @@ void GpuHevcEncoder::free_slot(FrameSlot& sl) {
     for (void* p : {(void*)b.fs, (void*)b.me.fs, (void*)b.me.mb, (void*)b.cu, (void*)b.coef, (void*)b.slice_data,
                     (void*)b.slice_len, (void*)b.slice_first, (void*)b.slice_of_cu, (void*)b.nslices, (void*)b.qpy, (void*)b.qp_pred, (void*)b.imode, (void*)b.itu4, (void*)b.cost, (void*)b.qpc,
                     (void*)b.sse_part, (void*)b.sse_tot, (void*)b.sao, (void*)b.slice_clk, (void*)b.tok, (void*)b.ntok, (void*)b.tok_off,
-                    (void*)b.tok_dense, (void*)b.wpp_ctx, (void*)b.wpp_flag, (void*)b.pack_done})
+                    (void*)b.tok_dense, (void*)b.wpp_ctx, (void*)b.wpp_flag, (void*)b.pack_done, (void*)b.isatd,
+                    (void*)b.igain, (void*)b.ipmode, (void*)b.isel})
         if (p) (void)hipFree(p);
     if (b.wpp_err) (void)hipHostFree(b.wpp_err);
     if (sl.fs_host) (void)hipHostFree(sl.fs_host);
@@ -293,10 +300,10 @@ void GpuHevcEncoder::enqueue_analysis_impl(bool idr, const uint8_t* src_y, const
     } else {
         h264::launch_hpel(geom_, sl.buf.me, hp_, hp_pitch_, stream_);
         h264::launch_me(geom_, sl.buf.me, src_y, stream_);
-        launch_hevc_inter(geom_, sl.buf, src_y, src_uv, stream_);
+        launch_hevc_inter(geom_, sl.buf, src_y, src_uv, stream_, cfg_.hevc_intra_in_p != 0);
     }
     launch_hevc_layout(geom_, sl.buf, idr, common_.max_slices(), cfg_.hevc_slice_cost, cfg_.hevc_deblock(), sl.fs_host->sao != 0, src_y,
-                       src_uv, stream_, cfg_.hevc_deblock_auto());
+                       src_uv, stream_, cfg_.hevc_deblock_auto(), cfg_.hevc_intra_in_p != 0);
 }
 
 void GpuHevcEncoder::link_entropy() {

@@ -115,6 +115,11 @@ class CpuHevcEncoder {
    private:
     void analyse_intra(const uint8_t* y, const uint8_t* uv, int pitch);
     void analyse_inter(const uint8_t* y, const uint8_t* uv, int pitch);
+    // EncoderConfig::hevc_intra_in_p: score, select and code the P picture's intra units (after the
+    // slice layout, before decide_ctb; k_hevc_intra_p_modes + k_hevc_intra_p)
+    void intra_in_p(const uint8_t* y, const uint8_t* uv, int pitch);
+    std::vector<uint32_t> inter_satd_;  // per unit: luma SATD of source - inter prediction
+    std::vector<uint8_t> intra_sel_;    // per unit: coded intra in this P picture
     int frame_qp_() { return qp_override_ >= 0 ? qp_override_ : common_.rc().cur_qp(); }
     int qp_override_ = -1;  // rate-control probe of the first picture
     // the picture's in-loop filter decision (EncoderConfig::deblock; adaptive: as k_hevc_db_auto)
@@ -144,8 +149,11 @@ class CpuHevcEncoder {
 // Per-frame kernel chain (hevc_kernels.hip):
 //   P: k_hpel -> k_me_full (shared with H.264) -> k_hevc_inter
 //   I: k_hevc_intra (one workgroup per slice, wavefront over its CTU rows)
-//   then k_hevc_layout (slices: rows for I, cost-balanced runs for P) -> k_hevc_decide (P:
-//   skip/merge/AMVP per slice) -> k_hevc_cabac (one wave per slice) -> k_hevc_pack
+//   then k_hevc_layout (slices: rows for I, cost-balanced runs for P) -> [P with
+//   EncoderConfig::hevc_intra_in_p: k_hevc_intra_p_modes (every unit's best intra mode against the
+//   inter reconstruction, its gain) -> k_hevc_intra_p (the locally best units coded intra over
+//   their inter reconstruction)] -> k_hevc_decide (P: skip/merge/AMVP per slice) -> k_hevc_qpy ->
+//   deblocking / SAO -> k_hevc_bins .. k_hevc_arith (one wave per slice) -> k_hevc_pack
 struct HevcFrameState {
     const uint8_t* ref_y;
     const uint8_t* ref_uv;
@@ -252,6 +260,11 @@ struct HevcDeviceBuffers {
     unsigned long long* sse_tot;  // [kSseSlots][kSseSlotWords] k_hevc_sao distortion totals (4 used per slot)
     uint32_t* pack_done;          // [1] k_hevc_pack workgroups finished (the last stamps t_end, re-arms it)
     uint32_t* db_state;           // [4] adaptive filter: the last P decision, counters, ticket (shared by the slots)
+    // intra units in P pictures (EncoderConfig::hevc_intra_in_p; nullptr without it)
+    uint32_t* isatd;              // [ncu] luma SATD of source - inter prediction (k_hevc_inter<true>)
+    int32_t* igain;               // [ncu] gain of coding the unit intra, 0: stays inter (k_hevc_intra_p_modes)
+    uint8_t* ipmode;              // [ncu] its best intra mode
+    uint8_t* isel;                // [ncu] the unit was coded intra (k_hevc_intra_p; k_hevc_decide reads it)
 };
 // Eager frames: one kernel stores both frame states (kernel arguments) to the device and stamps
 // the frame's start clock -- instead of two host-to-device copies (two blit kernels on the
@@ -261,15 +274,19 @@ void launch_hevc_publish(const HevcDeviceBuffers& b, const HevcFrameState& fs, c
 
 // IDR + temporal AQ: the source luma into fs->save_src (pointer read on the device)
 void launch_hevc_save_src(const Geometry& g, const HevcDeviceBuffers& b, const uint8_t* src_y, hipStream_t s);
+// intra_p (EncoderConfig::hevc_intra_in_p): also leaves every unit's inter SATD in b.isatd
 void launch_hevc_inter(const Geometry& g, const HevcDeviceBuffers& b, const uint8_t* src_y, const uint8_t* src_uv,
-                       hipStream_t s);
+                       hipStream_t s, bool intra_p = false);
 void launch_hevc_intra(const Geometry& g, const HevcDeviceBuffers& b, int slice_rows, int num_slices, int depth_intra,
                        const uint8_t* src_y, const uint8_t* src_uv, hipStream_t s);
 // Slice layout, per-slice decisions and (with deblock) the in-loop filter + final distortion:
 // runs on the analysis stream because the deblocked picture is the next frame's reference.
 // deblock_auto: k_hevc_db_auto decides the picture's filter first (EncoderConfig::deblock 2)
+// intra_p: P pictures run k_hevc_intra_p_modes and k_hevc_intra_p between the layout and the decisions
+// (EncoderConfig::hevc_intra_in_p); without it the launches are what they always were
 void launch_hevc_layout(const Geometry& g, const HevcDeviceBuffers& b, bool idr, int max_slices, int slice_cost, bool deblock,
-                        bool sao, const uint8_t* src_y, const uint8_t* src_uv, hipStream_t s, bool deblock_auto = false);
+                        bool sao, const uint8_t* src_y, const uint8_t* src_uv, hipStream_t s, bool deblock_auto = false,
+                        bool intra_p = false);
 void launch_hevc_entropy(const Geometry& g, const HevcDeviceBuffers& b, int max_slices, uint8_t* host_out,
                          hipStream_t s);
 

@@ -366,13 +366,49 @@ __device__ __forceinline__ void fill_cu(CuInfo& c, const TuResult& r) {
     c.csbf_c[1] = (uint8_t)r.csbf[2];
 }
 
+// 4x4 Hadamard SATD of all sixteen 4x4 blocks of a 16x16 residual on the matrix cores: with the
+// residual R (16 x 16) and H16 = diag(H4, H4, H4, H4) (H4 the order-4 Hadamard matrix,
+// symmetric), S = H16 R H16 holds every block's transform, SATD = sum |S|.  Two
+// v_mfma_f32_16x16x16_f16: T = R H16 (A = R), then S = H16 T, whose B operand layout
+// (lane l: rows 4(l>>4)..+3 of column l&15) is exactly T's accumulator layout, so T goes
+// across as four f16 conversions.  Exact: |R| <= 255 and |T| <= 1020 are integers f16 holds,
+// S (<= 4080) accumulates in f32.  The lane supplies the residual of row l & 15, columns
+// 4 (l >> 4) .. + 3 -- the A operand's layout.
+typedef _Float16 mf_h4 __attribute__((ext_vector_type(4)));
+typedef float mf_f4 __attribute__((ext_vector_type(4)));
+// H16[l & 15][4 (l >> 4) + j]: the B operand of the first product, the A of the second
+__device__ __forceinline__ mf_h4 hadamard16_operand(int lane) {
+    mf_h4 hm;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int row = lane & 15, k = (lane >> 4) * 4 + j;
+        // H4[a][b] = (-1)^(popcount(a & b)) for the order a = {++++, +-+-, ++--, +--+}
+        const int sgn = __popc((row & 3) & (k & 3)) & 1 ? -1 : 1;
+        hm[j] = (_Float16)((row >> 2) == (k >> 2) ? sgn : 0);
+    }
+    return hm;
+}
+__device__ __forceinline__ int satd16_wave(mf_h4 a, mf_h4 hm) {
+    const mf_f4 zero = {0.f, 0.f, 0.f, 0.f};
+    const mf_f4 t = __builtin_amdgcn_mfma_f32_16x16x16f16(a, hm, zero, 0, 0, 0);
+    mf_h4 tb;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) tb[i] = (_Float16)t[i];
+    const mf_f4 sm = __builtin_amdgcn_mfma_f32_16x16x16f16(hm, tb, zero, 0, 0, 0);
+    return wave_sum((int)(__builtin_fabsf(sm[0]) + __builtin_fabsf(sm[1]) + __builtin_fabsf(sm[2]) +
+                          __builtin_fabsf(sm[3])));
+}
+
 // ------------------------------------------------------------------ inter
+// kSatd (EncoderConfig::hevc_intra_in_p): the unit's luma SATD of source minus inter prediction goes
+// to isatd for k_hevc_intra_p_modes; the instance without it is the kernel as it always was
+template <bool kSatd>
 __global__ __launch_bounds__(256) void k_hevc_inter(Geometry g, const HevcFrameState* __restrict__ fs,
                                                      const h264::MbInfo* __restrict__ mbs,
                                                      const uint8_t* __restrict__ src_y,
                                                      const uint8_t* __restrict__ src_uv, CuInfo* __restrict__ cus,
                                                      int16_t* __restrict__ coef, uint32_t* __restrict__ cost,
-                                                     uint8_t* __restrict__ qp_coded) {
+                                                     uint8_t* __restrict__ qp_coded, uint32_t* __restrict__ isatd) {
     __shared__ Mats M;
     __shared__ TuBuf tb[4];
     __shared__ unsigned long long part[3][4];
@@ -498,6 +534,13 @@ __global__ __launch_bounds__(256) void k_hevc_inter(Geometry g, const HevcFrameS
         for (int comp = 0; comp < 2; ++comp) t.res[256 + comp * 64 + rc * 8 + cc] = 0;
     }
     wave_lds_sync();  // from here on every wave works alone (wave-local syncs, per-wave LDS)
+    if (kSatd) {  // the residual is in LDS: row lane & 15, columns 4 (lane >> 4) .. + 3 of it
+        mf_h4 a;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) a[j] = (_Float16)(valid ? (int)t.res[(lane & 15) * 16 + (lane >> 4) * 4 + j] : 0);
+        const int satd = satd16_wave(a, hadamard16_operand(lane));
+        if (valid && lane == 0) isatd[i] = (uint32_t)satd;
+    }
     int16_t* co = coef + (size_t)(valid ? i : 0) * kCoefPerCu;
     // option 1, one 16x16 luma TU (writes its levels and reconstruction; t.pred keeps the prediction)
     const TuResult r = code_tus<true>(t, M, qp, qpc, valid, co, fs->rec_y, g.pitch, fs->rec_uv, x0, y0, g.width,
@@ -815,26 +858,11 @@ __global__ __launch_bounds__(256) void k_hevc_intra_modes(Geometry g, const Hevc
     const int sdc = wave_sum(lane < 16 ? R.L[1 + lane] + R.T[1 + lane] : 0);
     if (lane == 0) R.dc = (sdc + 16) >> 5;
     wave_lds_sync();
-    // 4x4 Hadamard SATD of all sixteen 4x4 blocks of the unit on the matrix cores: with the
-    // residual R (16 x 16) and H16 = diag(H4, H4, H4, H4) (H4 the order-4 Hadamard matrix,
-    // symmetric), S = H16 R H16 holds every block's transform, SATD = sum |S|.  Two
-    // v_mfma_f32_16x16x16_f16 per mode: T = R H16 (A = R), then S = H16 T, whose B operand layout
-    // (lane l: rows 4(l>>4)..+3 of column l&15) is exactly T's accumulator layout, so T goes
-    // across as four f16 conversions.  Exact: |R| <= 255 and |T| <= 1020 are integers f16 holds,
-    // S (<= 4080) accumulates in f32.  The lane computes the residual of row l & 15, columns
-    // 4 (l >> 4) .. + 3 -- the A operand's layout.
-    typedef _Float16 mf_h4 __attribute__((ext_vector_type(4)));
-    typedef float mf_f4 __attribute__((ext_vector_type(4)));
+    // 4x4 Hadamard SATD on the matrix cores (satd16_wave), two products per mode: the lane computes
+    // the residual of row l & 15, columns 4 (l >> 4) .. + 3
     const int r = lane & 15, cb = (lane >> 4) * 4;
     const uint32_t sw = *reinterpret_cast<const uint32_t*>(src_y + (size_t)(y0 + r) * P + x0 + cb);
-    mf_h4 hm;  // H16[l & 15][4 (l >> 4) + j]: the B operand of the first product, the A of the second
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int row = lane & 15, k = cb + j;
-        // H4[a][b] = (-1)^(popcount(a & b)) for the order a = {++++, +-+-, ++--, +--+}
-        const int sgn = __popc((row & 3) & (k & 3)) & 1 ? -1 : 1;
-        hm[j] = (_Float16)((row >> 2) == (k >> 2) ? sgn : 0);
-    }
+    const mf_h4 hm = hadamard16_operand(lane);
     const mf_f4 zero = {0.f, 0.f, 0.f, 0.f};
     const int lambda = h264::lambda_sad(fs->qp);
     const uint64_t safe = fs->bl_safe;
@@ -845,14 +873,7 @@ __global__ __launch_bounds__(256) void k_hevc_intra_modes(Geometry g, const Hevc
         for (int j = 0; j < 4; ++j)
             a[j] = (_Float16)((int)((sw >> (8 * j)) & 0xff) -
                               pred_sample(m, 4, true, R.L, R.T, R.LF, R.TF, R.dc, cb + j, r));
-        const mf_f4 t = __builtin_amdgcn_mfma_f32_16x16x16f16(a, hm, zero, 0, 0, 0);
-        mf_h4 tb;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) tb[i] = (_Float16)t[i];
-        const mf_f4 sm = __builtin_amdgcn_mfma_f32_16x16x16f16(hm, tb, zero, 0, 0, 0);
-        const int sad = (int)(__builtin_fabsf(sm[0]) + __builtin_fabsf(sm[1]) + __builtin_fabsf(sm[2]) +
-                              __builtin_fabsf(sm[3]));
-        return wave_sum(sad) + lambda * intra_mode_bits(m, 1, 1);
+        return satd16_wave(a, hm) + lambda * intra_mode_bits(m, 1, 1);
     };
     const int best = intra_mode_search(cost);  // coarse-to-fine: at most 15 of the 35 modes
     int out = best, tu4 = 0;
@@ -884,14 +905,7 @@ __global__ __launch_bounds__(256) void k_hevc_intra_modes(Geometry g, const Hevc
             for (int j = 0; j < 4; ++j)
                 a[j] = (_Float16)((int)((sw >> (8 * j)) & 0xff) - pred_sample(m, 3, true, S.L[kq], S.T[kq], S.LF[kq],
                                                                                S.TF[kq], S.dc[kq], (cb + j) & 7, r & 7));
-            const mf_f4 t = __builtin_amdgcn_mfma_f32_16x16x16f16(a, hm, zero, 0, 0, 0);
-            mf_h4 tb;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) tb[i] = (_Float16)t[i];
-            const mf_f4 sm = __builtin_amdgcn_mfma_f32_16x16x16f16(hm, tb, zero, 0, 0, 0);
-            const int sad = (int)(__builtin_fabsf(sm[0]) + __builtin_fabsf(sm[1]) + __builtin_fabsf(sm[2]) +
-                                  __builtin_fabsf(sm[3]));
-            return wave_sum(sad) + lambda * intra_mode_bits(m, 1, 1);
+            return satd16_wave(a, hm) + lambda * intra_mode_bits(m, 1, 1);
         };
         const int best_s = intra_mode_search(cost_split);
         if (intra_split_wins(cost16, cost_split(best_s), lambda)) {
@@ -1483,6 +1497,222 @@ __global__ __launch_bounds__(64 * kMaxSliceRows) void k_hevc_intra(Geometry g, c
         fs->sse_part[lane * h264::kSsePartStride + y * split + seg] = lane == 0 ? acc[0] : (lane == 1 ? acc[1] : acc[2]);
 }
 
+// ------------------------------------------------------------------ intra units in P pictures
+// EncoderConfig::hevc_intra_in_p (hevc_core.h intra_p_*; CpuHevcEncoder::intra_in_p).  Both kernels
+// run after k_hevc_layout -- reference availability depends on the slices -- and before the in-loop
+// filters, on the unfiltered reconstruction k_hevc_inter left in fs->rec_y / rec_uv.
+//
+// References of a 16x16 unit at luma (x0, y0) (and, kChroma, of its two 8x8 chroma blocks) from that
+// reconstruction, the one-sample-per-lane pass of k_hevc_intra with the below-left segment as well:
+// reference q of the search order takes the sample ref_subst_idx names (8.4.4.2.2 in closed form)
+// straight from the picture at ref_pos -- only available segments are ever read, and those lie inside
+// the picture; then the [1 2 1]-filtered references (8.4.4.2.3) and the DC values.  avl: intra_p_avl.
+template <bool kChroma>
+__device__ __forceinline__ void unit_refs_from_rec(IntraRefs& R, const uint8_t* rec_y, const uint8_t* rec_uv, int P,
+                                                   int x0, int y0, int avl, int lane) {
+    for (int q = lane; q <= 64; q += 64) {
+        const int p = ref_subst_idx(q, 16, avl);
+        int v = 128;
+        if (p >= 0) {
+            int xx, yy;
+            ref_pos(p, 16, &xx, &yy);
+            v = rec_y[(size_t)(y0 + yy) * P + x0 + xx];
+        }
+        if (q < 32) R.L[32 - q] = v;
+        else if (q == 32) R.L[0] = R.T[0] = v;
+        else R.T[q - 32] = v;
+    }
+    if (kChroma)
+        for (int k = lane; k < 66; k += 64) {
+            const int comp = k >= 33 ? 1 : 0, q = k - 33 * comp;
+            const int p = ref_subst_idx(q, 8, avl);
+            int v = 128;
+            if (p >= 0) {
+                int xx, yy;
+                ref_pos(p, 8, &xx, &yy);
+                v = rec_uv[(size_t)(y0 / 2 + yy) * P + 2 * (x0 / 2 + xx) + comp];
+            }
+            if (q < 16) R.Lc[comp][16 - q] = v;
+            else if (q == 16) R.Lc[comp][0] = R.Tc[comp][0] = v;
+            else R.Tc[comp][q - 16] = v;
+        }
+    wave_lds_sync();
+    if (lane <= 32) {
+        const int k = lane;
+        if (k == 0) {
+            R.LF[0] = R.TF[0] = (R.L[1] + 2 * R.L[0] + R.T[1] + 2) >> 2;
+        } else if (k == 32) {
+            R.LF[32] = R.L[32];
+            R.TF[32] = R.T[32];
+        } else {
+            R.LF[k] = (R.L[k + 1] + 2 * R.L[k] + R.L[k - 1] + 2) >> 2;
+            R.TF[k] = (R.T[k + 1] + 2 * R.T[k] + R.T[k - 1] + 2) >> 2;
+        }
+    }
+    const int sl = lane < 16 ? R.L[1 + lane] + R.T[1 + lane] : 0;
+    const int dcl = (wave_sum(sl) + 16) >> 5;
+    int dc0 = 0, dc1 = 0;
+    if (kChroma) {
+        const int c0 = (lane >= 16 && lane < 24) ? R.Lc[0][lane - 15] + R.Tc[0][lane - 15] : 0;
+        const int c1 = (lane >= 24 && lane < 32) ? R.Lc[1][lane - 23] + R.Tc[1][lane - 23] : 0;
+        dc0 = (wave_sum(c0) + 8) >> 4;
+        dc1 = (wave_sum(c1) + 8) >> 4;
+    }
+    if (lane == 0) {
+        R.dc = dcl;
+        R.dcc[0] = dc0;
+        R.dcc[1] = dc1;
+    }
+    wave_lds_sync();
+}
+
+// Step 1, every unit scored: one wave per unit, a workgroup per CTB.  A unit whose inter SATD (isatd,
+// from k_hevc_inter<true>) is under the floor leaves with gain 0.  The others gather their references,
+// keep the lane's four source samples in registers and search the 35 modes coarse-to-fine
+// (intra_mode_search: at most 15 predictions, each one residual row segment per lane and two matrix
+// products, satd16_wave) for the lowest SATD + lambda * mode bits -- the neighbours are inter units, so
+// the MPM candidates are DC.  Out: the mode and intra_p_gain.
+__global__ __launch_bounds__(256) void k_hevc_intra_p_modes(Geometry g, const HevcFrameState* __restrict__ fs,
+                                                             const h264::MbInfo* __restrict__ mbs,
+                                                             const uint8_t* __restrict__ src_y,
+                                                             const CuInfo* __restrict__ cus,
+                                                             const uint32_t* __restrict__ isatd,
+                                                             const int* __restrict__ slice_first,
+                                                             const int* __restrict__ slice_of_ctb,
+                                                             uint8_t* __restrict__ ipmode, int32_t* __restrict__ igain) {
+    __shared__ IntraRefs rf[4];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int bid = blockIdx.x, cw = ctb_cols(g.mb_w);
+    const int x = 2 * (bid % cw) + (wave & 1), y = 2 * (bid / cw) + (wave >> 1);
+    if (x >= g.mb_w || y >= g.mb_h) return;  // wave-uniform; no workgroup barrier below
+    const int i = y * g.mb_w + x;
+    const int lambda = h264::lambda_sad(uni((int)cus[i].qp));
+    const uint32_t inter = (uint32_t)uni((int)isatd[i]);
+    if (!intra_p_candidate(inter, lambda)) {  // wave-uniform
+        if (lane == 0) igain[i] = 0;
+        return;
+    }
+    IntraRefs& R = rf[wave];
+    const int x0 = x * 16, y0 = y * 16, P = g.pitch;
+    const int avl = intra_p_avl(x, y, g.mb_w, g.mb_h, slice_first[slice_of_ctb[bid]]);
+    unit_refs_from_rec<false>(R, fs->rec_y, fs->rec_uv, P, x0, y0, avl, lane);
+    const int r = lane & 15, cb = (lane >> 4) * 4;  // the A operand's layout (satd16_wave)
+    const uint32_t sw = *reinterpret_cast<const uint32_t*>(src_y + (size_t)(y0 + r) * P + x0 + cb);
+    const mf_h4 hm = hadamard16_operand(lane);
+    auto cost = [&](int m) {
+        mf_h4 a;
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            a[j] = (_Float16)((int)((sw >> (8 * j)) & 0xff) -
+                              pred_sample(m, 4, true, R.L, R.T, R.LF, R.TF, R.dc, cb + j, r));
+        return satd16_wave(a, hm) + lambda * intra_mode_bits(m, 1, 1);
+    };
+    const int best = intra_mode_search(cost), bits = intra_mode_bits(best, 1, 1);
+    const int satd = cost(best) - lambda * bits;
+    if (lane == 0) {
+        constexpr int kStride = sizeof(h264::MbInfo) / sizeof(int16_t);
+        ipmode[i] = (uint8_t)best;
+        igain[i] = intra_p_gain(inter, intra_p_motion_bits(&mbs[0].mvx, kStride, x, y, g.mb_w), (uint32_t)satd, bits, lambda);
+    }
+}
+
+// Steps 2 and 3, selection and coding: one wave per CTB, four CTBs per workgroup.  Two units of a CTB
+// are neighbours, so a CTB holds at most one selected unit (intra_p_selected); the wave marks its
+// units in isel (k_hevc_decide reads it) and a workgroup without a selected unit leaves before the
+// transform matrices are built.  The selected unit is predicted again in the scored mode -- luma 16x16
+// and DM chroma 8x8, its neighbours still the inter reconstruction -- and goes through the TU pipeline
+// of the I pictures (code_tus<false>: core transforms, intra quantiser at the unit's class QP, dequant,
+// inverse), which writes the levels and the reconstruction over the inter ones; lane 0 rewrites the
+// CuInfo and the coded QP.  sse_delta: the distortion is summed from k_hevc_inter's per-CTB partials
+// (no in-loop filter, no SAO), so the unit's change goes into its CTB's partial.
+__global__ __launch_bounds__(256) void k_hevc_intra_p(Geometry g, const HevcFrameState* __restrict__ fs,
+                                                       const uint8_t* __restrict__ src_y,
+                                                       const uint8_t* __restrict__ src_uv,
+                                                       const int* __restrict__ slice_first,
+                                                       const int* __restrict__ slice_of_ctb,
+                                                       const uint8_t* __restrict__ ipmode,
+                                                       const int32_t* __restrict__ igain, CuInfo* __restrict__ cus,
+                                                       int16_t* __restrict__ coef, uint8_t* __restrict__ qp_coded,
+                                                       uint8_t* __restrict__ isel, int sse_delta) {
+    __shared__ Mats M;
+    __shared__ TuBuf tb[4];
+    __shared__ IntraRefs rf[4];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int cw = ctb_cols(g.mb_w), nctb = cw * ctb_rows(g.mb_h);
+    const int c = (int)blockIdx.x * 4 + wave;
+    int zsel = -1;
+    if (c < nctb)
+        for (int z = 0; z < 4; ++z) {
+            const int ux = 2 * (c % cw) + (z & 1), uy = 2 * (c / cw) + (z >> 1);
+            if (ux >= g.mb_w || uy >= g.mb_h) continue;
+            const bool sel = intra_p_selected(igain, g.mb_w, g.mb_h, ux, uy);  // wave-uniform
+            if (lane == 0) isel[uy * g.mb_w + ux] = sel ? 1 : 0;
+            if (sel) zsel = z;
+        }
+    if (!__syncthreads_or(zsel >= 0)) return;
+    fill_mats(M);
+    __syncthreads();
+    if (zsel < 0) return;  // wave-uniform; no workgroup barrier below
+    const int x = 2 * (c % cw) + (zsel & 1), y = 2 * (c / cw) + (zsel >> 1);
+    const int i = y * g.mb_w + x, x0 = x * 16, y0 = y * 16, P = g.pitch;
+    TuBuf& t = tb[wave];
+    IntraRefs& R = rf[wave];
+    const int mode = uni((int)ipmode[i]);
+    const int qp = uni((int)cus[i].qp);  // the class QP of the inter pass
+    const int qpc = chroma_qp(qp, fs->chroma_qp_offset);
+    const int avl = intra_p_avl(x, y, g.mb_w, g.mb_h, slice_first[slice_of_ctb[c]]);
+    // the lane's samples: luma row lane >> 2, columns 4 (lane & 3) .. + 3; chroma (lane & 7, lane >> 3)
+    const int r = lane >> 2, cb = (lane & 3) * 4, rc = lane >> 3, cc = lane & 7;
+    const uint32_t sy4 = *reinterpret_cast<const uint32_t*>(src_y + (size_t)(y0 + r) * P + x0 + cb);
+    const uint32_t sc2 = *reinterpret_cast<const uint16_t*>(src_uv + (size_t)(y0 / 2 + rc) * P + x0 + 2 * cc);
+    int old[3] = {0, 0, 0};  // the inter reconstruction's distortion over the display area
+    if (sse_delta) {
+        const uint32_t oy = *reinterpret_cast<const uint32_t*>(fs->rec_y + (size_t)(y0 + r) * P + x0 + cb);
+        const uint32_t oc = *reinterpret_cast<const uint16_t*>(fs->rec_uv + (size_t)(y0 / 2 + rc) * P + x0 + 2 * cc);
+        for (int j = 0; j < 4; ++j) {
+            const int d = (int)((sy4 >> (8 * j)) & 0xff) - (int)((oy >> (8 * j)) & 0xff);
+            old[0] += (x0 + cb + j < g.width && y0 + r < g.height) ? d * d : 0;
+        }
+        for (int comp = 0; comp < 2; ++comp) {
+            const int d = (int)((sc2 >> (8 * comp)) & 0xff) - (int)((oc >> (8 * comp)) & 0xff);
+            old[1 + comp] = (x0 + 2 * cc < g.width && y0 + 2 * rc < g.height) ? d * d : 0;
+        }
+    }
+    unit_refs_from_rec<true>(R, fs->rec_y, fs->rec_uv, P, x0, y0, avl, lane);
+    for (int j = 0; j < 4; ++j) {
+        const int p = pred_sample(mode, 4, true, R.L, R.T, R.LF, R.TF, R.dc, cb + j, r);
+        t.pred[r * 16 + cb + j] = (uint8_t)p;
+        t.res[r * 16 + cb + j] = (int16_t)((int)((sy4 >> (8 * j)) & 0xff) - p);
+    }
+    for (int comp = 0; comp < 2; ++comp) {
+        const int p = pred_sample(mode, 3, false, R.Lc[comp], R.Tc[comp], R.Lc[comp], R.Tc[comp], R.dcc[comp], cc, rc);
+        t.pred[256 + comp * 64 + rc * 8 + cc] = (uint8_t)p;
+        t.res[256 + comp * 64 + rc * 8 + cc] = (int16_t)((int)((sc2 >> (8 * comp)) & 0xff) - p);
+    }
+    wave_lds_sync();
+    const TuResult res = code_tus<false>(t, M, qp, qpc, true, coef + (size_t)i * kCoefPerCu, fs->rec_y, P, fs->rec_uv,
+                                         x0, y0, g.width, g.height);
+    if (sse_delta) {
+        const int o0 = wave_sum(old[0]), o1 = wave_sum(old[1]), o2 = wave_sum(old[2]);
+        if (lane < 3) {  // this wave owns the CTB's partial (modulo 2^64: the sum stays what k_hevc_pack expects)
+            const long long d = lane == 0 ? (long long)res.sse[0] - o0
+                                          : (lane == 1 ? (long long)res.sse[1] - o1 : (long long)res.sse[2] - o2);
+            fs->sse_part[lane * h264::kSsePartStride + c] += (unsigned long long)d;
+        }
+    }
+    if (lane == 0) {
+        CuInfo cu{};
+        cu.type = kCuIntra;
+        cu.intra_mode = (uint8_t)mode;
+        cu.qp = (uint8_t)qp;
+        fill_cu(cu, res);  // an unsplit tree (tu_split 0), whatever hevc_intra_split says
+        cu.ct = 1;
+        set_est_bytes(cu, res.bits);
+        cus[i] = cu;
+        qp_coded[i] = cu.cbf ? cu.qp : (uint8_t)255;
+    }
+}
+
 // ------------------------------------------------------------------ slice layout
 // One 1024-thread workgroup.  I pictures: fixed slices of slice_rows CTU rows.  P pictures:
 // cost-balanced raster runs (hevc_core.h plan_*): each thread owns a chunk of CUs; a wave-level
@@ -1614,10 +1844,13 @@ __global__ __launch_bounds__(1024) void k_hevc_layout(const HevcFrameState* __re
 }
 
 // Skip / merge / AMVP of the units of a P picture against their slice's neighbours and the coding
-// tree of every CTB (hevc_core.h decide_ctb): one thread per CTB.
+// tree of every CTB (hevc_core.h decide_ctb): one thread per CTB.  kIntraP: the picture may hold intra
+// units (isel, k_hevc_intra_p); the instance without it is the kernel as it always was.
+template <bool kIntraP>
 __global__ __launch_bounds__(256) void k_hevc_decide(Geometry g, const h264::MbInfo* __restrict__ mbs,
                                                       const int* __restrict__ slice_first,
-                                                      const int* __restrict__ slice_of_ctb, CuInfo* __restrict__ cus) {
+                                                      const int* __restrict__ slice_of_ctb, CuInfo* __restrict__ cus,
+                                                      const uint8_t* __restrict__ isel) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     const int cw = ctb_cols(g.mb_w);
     if (c >= cw * ctb_rows(g.mb_h)) return;
@@ -1631,7 +1864,8 @@ __global__ __launch_bounds__(256) void k_hevc_decide(Geometry g, const h264::MbI
         in[z] = x < g.mb_w && y < g.mb_h;
         if (in[z]) u[z] = cus[y * g.mb_w + x];
     }
-    decide_ctb(u, in, &mbs[0].mvx, kStride, x0, y0, g.mb_w, g.mb_h, slice_first[slice_of_ctb[c]]);
+    decide_ctb(u, in, &mbs[0].mvx, kStride, x0, y0, g.mb_w, g.mb_h, slice_first[slice_of_ctb[c]],
+               kIntraP ? isel : nullptr);
 #pragma unroll
     for (int z = 0; z < 4; ++z)
         if (in[z]) cus[(y0 + (z >> 1)) * g.mb_w + x0 + (z & 1)] = u[z];
@@ -2608,10 +2842,14 @@ void launch_hevc_save_src(const Geometry& g, const HevcDeviceBuffers& b, const u
 }
 
 void launch_hevc_inter(const Geometry& g, const HevcDeviceBuffers& b, const uint8_t* src_y, const uint8_t* src_uv,
-                       hipStream_t s) {
+                       hipStream_t s, bool intra_p) {
     const int nctb = ctb_cols(g.mb_w) * ctb_rows(g.mb_h);
-    hipLaunchKernelGGL(k_hevc_inter, dim3(nctb), dim3(256), 0, s, g, b.fs, b.me.mb, src_y, src_uv, b.cu, b.coef, b.cost,
-                       b.qpc);
+    if (intra_p)
+        hipLaunchKernelGGL(k_hevc_inter<true>, dim3(nctb), dim3(256), 0, s, g, b.fs, b.me.mb, src_y, src_uv, b.cu, b.coef,
+                           b.cost, b.qpc, b.isatd);
+    else
+        hipLaunchKernelGGL(k_hevc_inter<false>, dim3(nctb), dim3(256), 0, s, g, b.fs, b.me.mb, src_y, src_uv, b.cu, b.coef,
+                           b.cost, b.qpc, b.isatd);
 }
 
 void launch_hevc_intra(const Geometry& g, const HevcDeviceBuffers& b, int slice_rows, int num_slices, int depth_intra,
@@ -2628,14 +2866,23 @@ void launch_hevc_intra(const Geometry& g, const HevcDeviceBuffers& b, int slice_
 }
 
 void launch_hevc_layout(const Geometry& g, const HevcDeviceBuffers& b, bool idr, int max_slices, int slice_cost, bool deblock,
-                        bool sao, const uint8_t* src_y, const uint8_t* src_uv, hipStream_t s, bool deblock_auto) {
+                        bool sao, const uint8_t* src_y, const uint8_t* src_uv, hipStream_t s, bool deblock_auto,
+                        bool intra_p) {
     const int ncu = g.mb_w * g.mb_h;
     const int cw = ctb_cols(g.mb_w), nctb = cw * ctb_rows(g.mb_h);
     hipLaunchKernelGGL(k_hevc_layout, dim3((nctb + kScanTile - 1) / kScanTile), dim3(1024), 0, s, b.fs, b.cost, nctb, cw,
                        max_slices, slice_cost, b.slice_first, b.slice_of_cu, b.nslices);
-    if (!idr)
-        hipLaunchKernelGGL(k_hevc_decide, dim3((nctb + 255) / 256), dim3(256), 0, s, g, b.me.mb, b.slice_first,
-                           b.slice_of_cu, b.cu);
+    if (!idr && intra_p) {  // EncoderConfig::hevc_intra_in_p: score every unit, then select and code
+        hipLaunchKernelGGL(k_hevc_intra_p_modes, dim3(nctb), dim3(256), 0, s, g, b.fs, b.me.mb, src_y, b.cu, b.isatd,
+                           b.slice_first, b.slice_of_cu, b.ipmode, b.igain);
+        hipLaunchKernelGGL(k_hevc_intra_p, dim3((nctb + 3) / 4), dim3(256), 0, s, g, b.fs, src_y, src_uv, b.slice_first,
+                           b.slice_of_cu, b.ipmode, b.igain, b.cu, b.coef, b.qpc, b.isel, (!deblock && !sao) ? 1 : 0);
+        hipLaunchKernelGGL(k_hevc_decide<true>, dim3((nctb + 255) / 256), dim3(256), 0, s, g, b.me.mb, b.slice_first,
+                           b.slice_of_cu, b.cu, b.isel);
+    } else if (!idr) {
+        hipLaunchKernelGGL(k_hevc_decide<false>, dim3((nctb + 255) / 256), dim3(256), 0, s, g, b.me.mb, b.slice_first,
+                           b.slice_of_cu, b.cu, b.isel);
+    }
     // QpY chain: the deblocking filter's QP and the entropy coder's QP predictor
     hipLaunchKernelGGL(k_hevc_qpy, dim3(std::max(max_slices, ctb_rows(g.mb_h))), dim3(256), 0, s, g, b.fs, b.cu, b.qpc,
                        b.slice_first, b.nslices, b.qp_pred, b.qpy);

@@ -158,6 +158,9 @@ SCHEMA: list[Var] = [
     Var("hevc_intra_split", ["MXDESK_HEVC_INTRA_SPLIT"], 1, int,
         "HEVC I pictures, transform tree of a 16x16 unit: 0 = one 16x16 luma TU, 1 = may split into four 8x8 luma TUs, "
         "2 = and those into four 4x4 luma TUs (DST-VII)"),
+    Var("hevc_intra_in_p", ["MXDESK_HEVC_INTRA_IN_P"], 0, int,
+        "HEVC P pictures: 1 = a 16x16 unit may be coded intra from the reconstruction around it where that beats "
+        "its motion-compensated prediction, 0 = every unit is inter"),
     Var("vp8_tokens", ["MXDESK_VP8_TOKENS"], "host", str,
         "VP8 token partitions boolean-coded by: host (writer threads) | gpu (k_vp8_tokens; same stream)"),
     Var("subpel", ["MXDESK_SUBPEL"], True, bool, "quarter-pel motion refinement"),
@@ -274,6 +277,8 @@ class Config:
             raise ValueError("MXDESK_H264_PARTITIONS must be 0, 1 or 2")
         if v["hevc_intra_split"] not in (0, 1, 2):
             raise ValueError("MXDESK_HEVC_INTRA_SPLIT must be 0, 1 or 2")
+        if v["hevc_intra_in_p"] not in (0, 1):
+            raise ValueError("MXDESK_HEVC_INTRA_IN_P must be 0 or 1")
         if v["vp8_tokens"] not in ("host", "gpu"):
             raise ValueError("MXDESK_VP8_TOKENS must be host or gpu")
         if v["source"] not in ("auto", "synthetic", "x11"):
