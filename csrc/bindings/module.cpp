@@ -205,7 +205,8 @@ PYBIND11_MODULE(_native, m) {
         .def_readwrite("sao", &h264::EncoderConfig::sao)
         .def_readwrite("hevc_chroma_keep", &h264::EncoderConfig::hevc_chroma_keep)
         .def_readwrite("hevc_intra_split", &h264::EncoderConfig::hevc_intra_split)
-        .def_readwrite("hevc_intra_in_p", &h264::EncoderConfig::hevc_intra_in_p);
+        .def_readwrite("hevc_intra_in_p", &h264::EncoderConfig::hevc_intra_in_p)
+        .def_readwrite("hevc_transform_skip", &h264::EncoderConfig::hevc_transform_skip);
 
     py::class_<h264::FrameStats>(m, "FrameStats")
         .def_readonly("frame_index", &h264::FrameStats::frame_index)
@@ -428,7 +429,7 @@ PYBIND11_MODULE(_native, m) {
         .def_property_readonly("stats", &vp8::GpuVp8Encoder::last_stats);
 
     m.def("hevc_token_selftest", &hevc::token_selftest, py::arg("seed"), py::arg("slices"),
-          py::arg("intra_tu4") = false);
+          py::arg("intra_tu4") = false, py::arg("tskip") = false);
     // the 4x4 DST-VII of intra luma TUs on (n, 4, 4) int32 blocks: forward (residual -> coefficients)
     // or inverse (scaled coefficients -> residual), hevc_core.h fwd_dst4 / inv_dst4
     m.def(
@@ -522,6 +523,14 @@ PYBIND11_MODULE(_native, m) {
                      m(i, 5) = cus[i].tu4;
                  }
                  return a;
+             })
+        // per 16x16 unit: the coded 4x4 luma TUs sent with transform_skip_flag 1 (bit 4k + j = TU j of
+        // node k; EncoderConfig::hevc_transform_skip)
+        .def("cu_tskip",
+             [](hevc::CpuHevcEncoder& e) {
+                 std::vector<int> t;
+                 for (const auto& c : e.cus()) t.push_back(c.tskip);
+                 return t;
              })
         .def_property_readonly("slice_rows", [](hevc::CpuHevcEncoder& e) { return e.common().slice_rows(); })
         .def_property_readonly("level_idc", [](hevc::CpuHevcEncoder& e) { return e.common().level_idc(); })

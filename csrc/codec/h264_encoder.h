@@ -117,6 +117,12 @@ struct EncoderConfig {
     // intra_p_gain); the units chosen in one picture never touch each other (intra_p_selected).  0: every
     // unit of a P picture is inter, the streams are what they always were.  (intra_in_p above is H.264's.)
     int hevc_intra_in_p = 0;
+    // HEVC P pictures: a 4x4 luma TU of the inter transform tree (tu_split 2) may be coded with
+    // transform_skip_flag 1 -- the residual quantised as it stands, no transform -- where that beats the
+    // transformed coding of the same samples by SSE + lambda * bits (hevc_core.h split_encode).  The PPS
+    // then sets transform_skip_enabled_flag and every coded 4x4 TU of every picture sends the flag.
+    // 0: the flag is off, the streams are what they always were.
+    int hevc_transform_skip = 0;
     int hevc_slice_cost = 1536;  // HEVC without WPP: P-picture slice work target (hevc_core.h cu_cost units)
     // HEVC wavefront parallel processing (entropy_coding_sync_enabled_flag): P pictures in slices of
     // hevc_wpp_rows CTU rows, every CTU row its own CABAC substream (one GPU wave each) that starts

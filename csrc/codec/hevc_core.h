@@ -501,7 +501,8 @@ enum Ctx : int {
     C_SPLIT_CU = 139,      // 3
     C_SAO_MERGE = 142,     // 1 (sao_merge_left_flag and sao_merge_up_flag)
     C_SAO_TYPE = 143,      // 1 (first bin of sao_type_idx_luma / _chroma)
-    C_NUM = 144
+    C_TSKIP = 144,         // 2 (transform_skip_flag: luma, chroma)
+    C_NUM = 146
 };
 
 // initValue per initType (0: I, 1: P without cabac_init_flag, 2: B), Tables 9-5..9-37
@@ -524,7 +525,8 @@ constexpr uint8_t kCtxInit[3][C_NUM] = {
      138, 153, 136, 167, 152, 152,
      153, 138, 138,
      139, 141, 157,
-     153, 200},
+     153, 200,
+     139, 139},
     {// P (initType 1)
      197, 185, 201,
      110, 122, 149,
@@ -543,7 +545,8 @@ constexpr uint8_t kCtxInit[3][C_NUM] = {
      107, 167, 91, 122, 107, 167,
      124, 138, 94,
      107, 139, 126,
-     153, 185},
+     153, 185,
+     139, 139},
     {// B (initType 2)
      197, 185, 201,
      154, 137, 134,
@@ -562,7 +565,8 @@ constexpr uint8_t kCtxInit[3][C_NUM] = {
      107, 167, 91, 107, 107, 167,
      224, 167, 122,
      107, 139, 126,
-     153, 160}};
+     153, 160,
+     139, 139}};
 
 // Context state byte: (pStateIdx << 1) | valMps (9.3.2.2)
 MXHD uint8_t ctx_init_state(int init_value, int qp) {
@@ -789,7 +793,10 @@ struct CuInfo {
     // coded flags of those 4x4 TUs (bit 4k + j)
     uint8_t tu4;
     uint16_t cbf_y16;
-    uint8_t rsv[4];
+    // EncoderConfig::hevc_transform_skip: bit 4k + j = the coded 4x4 luma TU j of node k (tu4 bit k) is
+    // transform-skipped (transform_skip_flag 1); 0 wherever tu4 is 0
+    uint16_t tskip;
+    uint8_t rsv[2];
 };
 static_assert(sizeof(CuInfo) == 32, "CuInfo layout");
 constexpr int kCuWords = (int)(sizeof(CuInfo) / 4);
@@ -818,6 +825,7 @@ MXHD void cu_summarise(CuInfo& c, const int16_t* co) {
     if (c.tu_split != 2) {
         c.tu4 = 0;
         c.cbf_y16 = 0;
+        c.tskip = 0;
         if (tu_summary(co, 256, &c.last[0], &m)) c.cbf |= 1;
         c.csbf_y = (uint16_t)m;
         if (tu_summary(co + 256, 64, &c.last[1], &m)) c.cbf |= 2;
@@ -845,6 +853,7 @@ MXHD void cu_summarise(CuInfo& c, const int16_t* co) {
         }
     }
     c.cbf |= c.cbf_y4 ? 1 : 0;
+    c.tskip &= c.cbf_y16;  // only coded 4x4 TUs carry the flag
     c.last[0] = (uint8_t)(lsum ? (lsum > 256 ? 255 : lsum - 1) : 0);
     c.csbf_y = (uint16_t)csy;
     for (int comp = 0; comp < 2; ++comp) {
@@ -945,6 +954,7 @@ struct TuDesc {
     int sb0, log2n, cidx, last_idx;
     uint32_t csbf_mask;
     int scan;  // scanIdx (intra_scan_idx for intra 4x4 / 8x8 luma and 4x4 chroma TUs, else 0)
+    int ts;    // transform_skip_flag of a 4x4 TU while the PPS enables it; -1: not sent
 };
 // coded (or inferred: DC and last) sub-blocks of a TU as a raster mask
 MXHD uint32_t tu_csbf_raster(const TuDesc& t) {
@@ -958,9 +968,11 @@ MXHD uint32_t tu_csbf_raster(const TuDesc& t) {
     return r;
 }
 
-// last_sig_coeff_x / _y prefix and suffix of a TU (the vertical scan codes the pair swapped)
+// transform_skip_flag (4x4 TUs, pps transform_skip_enabled_flag), then last_sig_coeff_x / _y prefix
+// and suffix of a TU (the vertical scan codes the pair swapped)
 template <class E, class Ctx>
 MXHD void code_tu_last(E& e, Ctx& ctx, const TuDesc& t) {
+    if (t.ts >= 0) e.bin(ctx, C_TSKIP + (t.cidx ? 1 : 0), t.ts);  // residual_coding starts with it (7.3.8.11)
     int lx, ly;
     if (t.scan == 2)
         scan_pos_s(t.log2n, t.scan, t.last_idx, &ly, &lx);
@@ -1310,10 +1322,12 @@ MXHD bool split_tu_coded(const CuInfo& c, int k, int t) {
 MXHD int split_tu_sb0(int k, int t) { return t == 0 ? 4 * k : (t == 1 ? 16 + k : 20 + k); }
 // scanIdx of the split tree's TUs of CU c (8x8 / 4x4 luma and 4x4 chroma; DM chroma)
 MXHD int split_scan(const CuInfo& c) { return c.type == kCuIntra ? intra_scan_idx(c.intra_mode) : 0; }
-// TU descriptor of a split child's TU / an unsplit unit's TU
+// TU descriptor of a split child's TU / an unsplit unit's TU.  ts4: transform_skip_flag of a 4x4 TU
+// (chroma: never skipped, 0 while the flag is sent, unit_ts4; -1 when it is not sent)
 template <class Cf>
-MXHD TuDesc split_tu_desc(const Cf& cf, int k, int t, int scan) {
+MXHD TuDesc split_tu_desc(const Cf& cf, int k, int t, int scan, int ts4) {
     TuDesc d;
+    d.ts = t == 0 ? -1 : ts4;
     d.sb0 = split_tu_sb0(k, t);
     d.log2n = t == 0 ? 3 : 2;
     d.cidx = t;
@@ -1323,8 +1337,9 @@ MXHD TuDesc split_tu_desc(const Cf& cf, int k, int t, int scan) {
 }
 // the 4x4 luma TU j of split child k (one sub-block: 4k + j)
 template <class Cf>
-MXHD TuDesc luma4_tu_desc(const Cf& cf, int k, int j, int scan) {
+MXHD TuDesc luma4_tu_desc(const Cf& cf, int k, int j, int scan, int ts4) {
     TuDesc d;
+    d.ts = ts4;
     d.sb0 = 4 * k + j;
     d.log2n = 2;
     d.cidx = 0;
@@ -1335,6 +1350,7 @@ MXHD TuDesc luma4_tu_desc(const Cf& cf, int k, int j, int scan) {
 MXHD TuDesc flat_tu_desc(const CuInfo& c, int t) {
     TuDesc d;
     d.scan = 0;
+    d.ts = -1;  // 16x16 and 8x8 TUs
     d.sb0 = t == 0 ? 0 : (t == 1 ? 16 : 20);
     d.log2n = t == 0 ? 4 : 3;
     d.cidx = t;
@@ -1364,14 +1380,20 @@ struct UnitSyn {
     MXHD int depth_of(const CuInfo& c) const { return c.type == kCuIntra ? depth_intra : depth_inter; }
     bool sao_on, has_l, has_u;
     uint32_t sao[3], sao_l[3], sao_u[3];
+    bool tskip;        // pps transform_skip_enabled_flag: every coded 4x4 TU sends transform_skip_flag
+    // the flag of the unit's 4x4 luma TU j of node k / of its 4x4 chroma TUs (-1: not sent)
+    MXHD int ts4_luma(const CuInfo& c, int k, int j) const { return tskip ? (c.tskip >> (4 * k + j)) & 1 : -1; }
+    MXHD int ts4_chroma() const { return tskip ? 0 : -1; }
 };
 
 // Build the syntax context of unit (x, y) of a slice of CTBs [first_ctb, end_ctb).  get(u): CuInfo
 // of raster unit u; sao: 4 words per CTB (nullptr: SAO off); qp_pred: the unit's QP predictor.
 template <class Get>
 MXHD UnitSyn unit_syn(const Get& get, const uint32_t* sao, int x, int y, int mb_w, int mb_h, bool islice,
-                      int first_ctb, int end_ctb, bool wpp, int depth_inter, int depth_intra, int qp_pred) {
+                      int first_ctb, int end_ctb, bool wpp, int depth_inter, int depth_intra, int qp_pred,
+                      bool tskip = false) {
     UnitSyn u;
+    u.tskip = tskip;
     const int cw = ctb_cols(mb_w);
     const int c = ctb_of(x, y, cw), z = ((y & 1) << 1) | (x & 1);
     const int x0 = x & ~1, y0 = y & ~1;
@@ -1733,7 +1755,9 @@ constexpr int kTokBypassMax = 11;
 // the last-position, CU and SAO syntax.  Sixteen 4x4 luma TUs (inter tu4, or intra with tree depth 2,
 // whose levels are never decimated) keep the 24 sub-blocks and add, over the 256: 24 last positions of at
 // most 6 context bins + 2 suffix tokens, 16 + 4 cbf_luma, 4 x 3 child flags -- under 230 with the
-// largest head (an AMVP CU with SAO); an intra head is smaller.
+// largest head (an AMVP CU with SAO); an intra head is smaller.  With transform_skip_enabled_flag
+// each of those 24 TUs sends one transform_skip_flag more: under 254, still inside the 256 (a TU's
+// last-position part grows to 15 tokens, far below kPartTokens).
 constexpr uint32_t kMaxCuTokens = 24 * 108 + 256;
 
 // Records bins as tokens (same interface as CabacEnc).  Consecutive bypass bins are merged.
@@ -1831,7 +1855,7 @@ MXHD int for_each_part(const CuInfo& c, const UnitSyn& u, const Cf& cf, F f) {
 #pragma unroll 1
             for (int j = 0; j < 4; ++j) {
                 const bool coded = (c.cbf_y16 >> (4 * k + j)) & 1;
-                if (coded) pt.d = luma4_tu_desc(cf, k, j, split_scan(c));
+                if (coded) pt.d = luma4_tu_desc(cf, k, j, split_scan(c), u.ts4_luma(c, k, j));
                 pt.k = k;
                 pt.t = j;
                 pt.kind = kPartGrand;
@@ -1847,7 +1871,7 @@ MXHD int for_each_part(const CuInfo& c, const UnitSyn& u, const Cf& cf, F f) {
         for (int t = s4 ? 1 : 0; t < 3; ++t) {
             const bool coded = kind == kResSplit ? split_tu_coded(c, k, t) : (((c.cbf >> t) & 1) != 0);
             if (!coded) continue;
-            pt.d = kind == kResSplit ? split_tu_desc(cf, k, t, split_scan(c)) : flat_tu_desc(c, t);
+            pt.d = kind == kResSplit ? split_tu_desc(cf, k, t, split_scan(c), u.ts4_chroma()) : flat_tu_desc(c, t);
             pt.k = k;
             pt.t = t;
             pt.kind = kPartTuLast;
@@ -1911,11 +1935,13 @@ MXHD void code_unit_direct(E& e, Ctx& ctx, const CuInfo& c, const UnitSyn& u, co
             if (s4)
                 for (int j = 0; j < 4; ++j) {
                     code_unit_grand(e, ctx, c, u, k, j);
-                    if ((c.cbf_y16 >> (4 * k + j)) & 1) code_residual(e, ctx, cf, luma4_tu_desc(cf, k, j, split_scan(c)));
+                    if ((c.cbf_y16 >> (4 * k + j)) & 1)
+                        code_residual(e, ctx, cf, luma4_tu_desc(cf, k, j, split_scan(c), u.ts4_luma(c, k, j)));
                 }
 #pragma unroll 1
             for (int t = s4 ? 1 : 0; t < 3; ++t)
-                if (split_tu_coded(c, k, t)) code_residual(e, ctx, cf, split_tu_desc(cf, k, t, split_scan(c)));
+                if (split_tu_coded(c, k, t))
+                    code_residual(e, ctx, cf, split_tu_desc(cf, k, t, split_scan(c), u.ts4_chroma()));
         }
     } else if (kind == kResFlat) {
 #pragma unroll 1
@@ -1935,6 +1961,7 @@ struct PicSyn {
     int mb_w, mb_h;
     int depth_inter;  // max_transform_hierarchy_depth_inter
     int depth_intra;  // max_transform_hierarchy_depth_intra
+    bool tskip = false;  // pps transform_skip_enabled_flag (EncoderConfig::hevc_transform_skip)
 };
 struct ArrGet {  // raster CuInfo lookup for unit_syn
     const CuInfo* p;
@@ -1942,7 +1969,7 @@ struct ArrGet {  // raster CuInfo lookup for unit_syn
 };
 MXHD UnitSyn pic_unit_syn(const PicSyn& ps, int x, int y, bool islice, int first, int end, bool wpp) {
     return unit_syn(ArrGet{ps.cus}, ps.sao, x, y, ps.mb_w, ps.mb_h, islice, first, end, wpp, ps.depth_inter,
-                    ps.depth_intra, ps.qp_pred[y * ps.mb_w + x]);
+                    ps.depth_intra, ps.qp_pred[y * ps.mb_w + x], ps.tskip);
 }
 
 // Entropy-code CTB c of the slice [first, end) into e: every unit inside the picture, in z order,
@@ -2262,6 +2289,45 @@ MXHD int tu4_intra_encode(const int* res, int qp, int16_t* levels, int* rres, in
     return nz;
 }
 
+// Transform skip of a 4x4 TU (8.6.4.2 with transform_skip_flag, 8-bit video): the residual stands in
+// for the coefficients, scaled by the transform's gain -- forward res << 5 (15 - bitDepth - log2 4),
+// back (d << tsShift 7, + 2048) >> bdShift 12.  No rotation and no RDPCM in version 1.
+MXHD int tskip_fwd(int res) { return res * 32; }
+MXHD int tskip_inv(int d) { return (d * 128 + 2048) >> 12; }
+// A 4x4 inter luma TU coded with transform_skip_flag 1: tu_encode_t<2> with the two functions above in
+// place of the transforms.  Levels keep the diagonal scan order, and the decimation and trailing-trim
+// rules apply as they do to transformed levels (they price scan positions, not frequencies).
+MXHD int tu4_skip_encode(const int* res, int qp, int16_t* levels, int* rres) {
+    int nz = 0, mx = 0;
+    for (int v = 0; v < 4; ++v)
+        for (int u = 0; u < 4; ++u) {
+            const int l = quant_coef(tskip_fwd(res[v * 4 + u]), qp, 2, false);
+            levels[scan_index(2, u, v)] = (int16_t)l;
+            nz += l != 0;
+            mx = (l < 0 ? -l : l) > mx ? (l < 0 ? -l : l) : mx;
+        }
+    if (tu_decimate(2, false, nz, mx))
+        for (int i = 0; i < 16; ++i) levels[i] = 0;
+    for (int it = 0; it < kTrimIters; ++it) {
+        int last = -1, prev = -1;
+        for (int i = 0; i < 16; ++i)
+            if (levels[i]) {
+                prev = last;
+                last = i;
+            }
+        if (last < 0 || (levels[last] != 1 && levels[last] != -1) || last - prev <= kTrimGap) break;
+        levels[last] = 0;
+    }
+    nz = 0;
+    for (int v = 0; v < 4; ++v)
+        for (int u = 0; u < 4; ++u) {
+            const int l = levels[scan_index(2, u, v)];
+            nz += l != 0;
+            rres[v * 4 + u] = tskip_inv(dequant_coef(l, qp, 2));
+        }
+    return nz;
+}
+
 // lambda for SSE decisions, HM's 0.57 * 2^((QP-12)/3), in 1/16 units (integer: CPU == GPU)
 constexpr uint32_t kLambdaSse16[52] = {1,    1,    1,    1,    1,    2,     2,     3,     4,     5,     6,
                                        7,    9,    11,   14,   18,   23,    29,    36,    46,    58,    73,
@@ -2302,10 +2368,15 @@ MXHD bool choose_split(uint64_t sse16, uint32_t bits16, uint64_t sse8, uint32_t 
 // With try4 a luma node is also coded as four 4x4 TUs (sub-block 4k + j = the 4x4 block (j & 1,
 // j >> 1) of the node) and keeps them when their luma SSE + lambda * bits is lower (choose_split,
 // the node's own distortion against pred + res); returns the mask of such nodes (CuInfo::tu4).
+// With tskip (EncoderConfig::hevc_transform_skip) every such 4x4 TU is coded both ways, transformed
+// and transform-skipped, and keeps the skip coding when choose_split prefers it over the TU's own
+// samples (both pay the flag's bit); the node's decision then runs on the winners.  *tskip: the coded
+// skipped TUs of the nodes in the returned mask (CuInfo::tskip, bit 4k + j).
 MXHD int split_encode(const int* res, const int (*rc)[64], int qp, int qpc, int16_t* co, int* rr, int (*rrc)[64],
-                      const int* pred = nullptr, bool try4 = false) {
+                      const int* pred = nullptr, bool try4 = false, int* tskip = nullptr) {
     int blk[64], rb[64];
     int tu4 = 0;
+    if (tskip) *tskip = 0;
     for (int k = 0; k < 4; ++k) {
         const int bx = (k & 1) * 8, by = (k >> 1) * 8;
         for (int r = 0; r < 8; ++r)
@@ -2316,11 +2387,29 @@ MXHD int split_encode(const int* res, const int (*rc)[64], int qp, int qpc, int1
         if (!try4 || !split_worth_trying(tu_levels(co + 64 * k, 64))) continue;
         int16_t l4[64];
         int r4[64], b4[16], rb4[16];
+        int sk = 0;  // the node's skipped TUs
         for (int j = 0; j < 4; ++j) {
             const int jx = (j & 1) * 4, jy = (j >> 1) * 4;
             for (int r = 0; r < 4; ++r)
                 for (int q = 0; q < 4; ++q) b4[r * 4 + q] = blk[(jy + r) * 8 + jx + q];
             tu_encode(2, b4, qp, false, l4 + 16 * j, rb4);
+            if (tskip) {
+                int16_t ls[16];
+                int rs[16];
+                const int nzs = tu4_skip_encode(b4, qp, ls, rs);
+                uint64_t sd = 0, ss = 0;
+                for (int r = 0; r < 4; ++r)
+                    for (int q = 0; q < 4; ++q) {
+                        const int o = (by + jy + r) * 16 + bx + jx + q, src = pred[o] + res[o];
+                        const int ed = src - clip255(pred[o] + rb4[r * 4 + q]), es = src - clip255(pred[o] + rs[r * 4 + q]);
+                        sd += (uint64_t)(ed * ed);
+                        ss += (uint64_t)(es * es);
+                    }
+                if (choose_split(sd, tu_bits_est(l4 + 16 * j, 16) + 1, ss, tu_bits_est(ls, 16) + 1, qp)) {
+                    for (int i = 0; i < 16; ++i) l4[16 * j + i] = ls[i], rb4[i] = rs[i];
+                    if (nzs) sk |= 1 << j;
+                }
+            }
             for (int r = 0; r < 4; ++r)
                 for (int q = 0; q < 4; ++q) r4[(jy + r) * 8 + jx + q] = rb4[r * 4 + q];
         }
@@ -2336,6 +2425,7 @@ MXHD int split_encode(const int* res, const int (*rc)[64], int qp, int qpc, int1
         for (int j = 0; j < 4; ++j) b4bits += tu_bits_est(l4 + 16 * j, 16);
         if (choose_split(s8, tu_bits_est(co + 64 * k, 64), s4, b4bits, qp)) {
             tu4 |= 1 << k;
+            if (tskip) *tskip |= sk << (4 * k);
             for (int i = 0; i < 64; ++i) co[64 * k + i] = l4[i];
             for (int r = 0; r < 8; ++r)
                 for (int q = 0; q < 8; ++q) rr[(by + r) * 16 + bx + q] = r4[r * 8 + q];
@@ -2805,7 +2895,9 @@ MXHD void set_est_bytes(CuInfo& c, uint32_t bits) { c.est_bytes = c.cbf ? est_by
 // Below this much work per slice, fewer slices: 1536 tokens keep a slice near 0.25 ms; the level's
 // slice limit usually binds first at 4K.
 constexpr uint32_t kCostPerSlice = 1536;  // EncoderConfig::hevc_slice_cost default
-// Largest cu_cost (last+1 <= 256 + 64 + 64, 16 + 4 + 4 sub-blocks, est_bytes <= 255).
+// Largest cu_cost (last+1 <= 256 + 64 + 64, 16 + 4 + 4 sub-blocks, est_bytes <= 255).  The up to 24
+// transform_skip_flag bins of a unit (hevc_transform_skip) do not enter the model: est_bytes is
+// capped, so the bound holds with them.
 constexpr uint32_t kMaxCuCost = ((2u * 384u + 104u * 24u + 31u * 255u) >> 3) - 4u;
 // Slices are laid out in whole CTBs: the largest CTB cost (four units)
 constexpr uint32_t kMaxCtbCost = 4u * kMaxCuCost;

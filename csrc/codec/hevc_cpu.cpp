@@ -244,7 +244,7 @@ void HevcCommon::write_parameter_sets(std::vector<uint8_t>& out) const {
         w.ue(0);      // num_ref_idx_l1_default_active_minus1
         w.se(0);      // init_qp_minus26
         w.put(0, 1);  // constrained_intra_pred_flag
-        w.put(0, 1);  // transform_skip_enabled_flag
+        w.put(c.hevc_transform_skip ? 1 : 0, 1);  // transform_skip_enabled_flag (4x4 TUs: no range extension)
         w.put(1, 1);  // cu_qp_delta_enabled_flag
         w.ue(kCtbLog2 - 4);  // diff_cu_qp_delta_depth: 16x16 quantization groups
         w.se(c.chroma_qp_offset);  // pps_cb_qp_offset
@@ -762,7 +762,9 @@ void CpuHevcEncoder::analyse_inter(const uint8_t* sy, const uint8_t* suv, int pi
                 // 4x4 chroma TUs; keep the cheaper by SSE + lambda * bits
                 int16_t co2[kCoefPerCu];
                 int rr2[256], rrc2[2][64];
-                const int tu4 = split_encode(res, rc, qp, qpc, co2, rr2, rrc2, pred, cfg_.tu_split >= 2);
+                int ts = 0;
+                const int tu4 = split_encode(res, rc, qp, qpc, co2, rr2, rrc2, pred, cfg_.tu_split >= 2,
+                                             cfg_.hevc_transform_skip ? &ts : nullptr);
                 uint64_t sse1 = 0, sse2 = 0;
                 for (int k = 0; k < 256; ++k) {
                     const int s0 = pred[k] + res[k];
@@ -781,6 +783,7 @@ void CpuHevcEncoder::analyse_inter(const uint8_t* sy, const uint8_t* suv, int pi
                 if (choose_split(sse1, cu_bits_est(co, false), sse2, cu_bits_est(co2, true, tu4), qp)) {
                     c.tu_split = 2;
                     c.tu4 = (uint8_t)tu4;
+                    c.tskip = (uint16_t)ts;
                     std::memcpy(co, co2, sizeof co2);
                     std::memcpy(rr, rr2, sizeof rr2);
                     std::memcpy(rrc, rrc2, sizeof rrc2);
@@ -800,6 +803,7 @@ void CpuHevcEncoder::analyse_inter(const uint8_t* sy, const uint8_t* suv, int pi
                     for (int k = 0; k < 256; ++k) co[k] = 0, rr[k] = 0;
                     c.tu_split = cfg_.tu_split ? 1 : 0;
                     c.tu4 = 0;
+                    c.tskip = 0;
                 }
             }
             for (int r = 0; r < 16; ++r)
@@ -897,7 +901,7 @@ const std::vector<uint8_t>& CpuHevcEncoder::encode(const uint8_t* y, const uint8
         slices_ = common_.row_slices();
         qp_chain(qp_override_);
         const PicSyn ps{cu_.data(), coef_.data(), qp_pred_.data(), nullptr, W, H, common_.depth_inter(),
-                        common_.depth_intra()};
+                        common_.depth_intra(), cfg_.hevc_transform_skip != 0};
         std::vector<uint8_t> buf;
         std::vector<uint32_t> sub_len;
         uint8_t ctx[C_NUM];
@@ -981,7 +985,7 @@ const std::vector<uint8_t>& CpuHevcEncoder::encode(const uint8_t* y, const uint8
     std::vector<uint32_t> sub_len;
     uint8_t ctx[C_NUM];
     const PicSyn ps{cu_.data(), coef_.data(), qp_pred_.data(), cfg_.sao ? sao_.data() : nullptr, W, H,
-                    common_.depth_inter(), common_.depth_intra()};
+                    common_.depth_inter(), common_.depth_intra(), cfg_.hevc_transform_skip != 0};
     for (size_t s = 0; s < slices_.size(); ++s) {
         const int first = slices_[s], end = slice_end(s);
         const uint32_t cap = (uint32_t)(end - first) * 4096 + 1024;
@@ -1034,8 +1038,10 @@ namespace hevc {
 // levels up to the escape range, SAO parameters) coded twice -- directly and through the
 // bin-token path -- must give identical bytes.  Returns the number of slices checked; throws on
 // the first mismatch.  intra_tu4: intra units carry 4x4 luma nodes as well, under
-// max_transform_hierarchy_depth_intra 2 (the default draws the same slices as before).
-int token_selftest(uint32_t seed, int slices, bool intra_tu4) {
+// max_transform_hierarchy_depth_intra 2 (the default draws the same slices as before).  tskip:
+// transform_skip_enabled_flag -- every coded 4x4 TU sends transform_skip_flag, with random skip masks
+// on the 4x4 luma TUs (without it nothing more is drawn: the slices are as before).
+int token_selftest(uint32_t seed, int slices, bool intra_tu4, bool tskip) {
     uint32_t r = seed * 2654435761u + 1u;
     auto rnd = [&r](uint32_t n) {
         r ^= r << 13;
@@ -1097,6 +1103,7 @@ int token_selftest(uint32_t seed, int slices, bool intra_tu4) {
                 cu.tu_split = (uint8_t)(1 + rnd(2));  // intra too (max_transform_hierarchy_depth_intra 1 or 2 below)
                 // 8x8 nodes into 4x4 TUs (intra units with intra_tu4 only)
                 cu.tu4 = (cu.tu_split == 2 && (intra_tu4 || cu.type != kCuIntra)) ? (uint8_t)rnd(16) : 0;
+                if (tskip && cu.tu4 && cu.type != kCuSkip) cu.tskip = (uint16_t)rnd(65536);  // cu_summarise keeps the coded TUs' bits
                 if (cu.type != kCuSkip) fill_levels(cu, i);
                 qpp[(size_t)i] = (uint8_t)(10 + rnd(40));
             }
@@ -1111,7 +1118,7 @@ int token_selftest(uint32_t seed, int slices, bool intra_tu4) {
         }
         const bool use_sao = rnd(2) != 0;
         const PicSyn ps{cus.data(), coef.data(), qpp.data(), use_sao ? sao.data() : nullptr, mb_w, mb_h,
-                        rnd(2) ? 3 : 0, intra_tu4 ? 2 : 1};
+                        rnd(2) ? 3 : 0, intra_tu4 ? 2 : 1, tskip};
         const uint32_t cap = (uint32_t)(end - first) * 16384 + 1024;
         std::vector<uint8_t> a(cap), b(cap);
         std::vector<uint16_t> tok(kMaxCuTokens);

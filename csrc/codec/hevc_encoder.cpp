@@ -207,6 +207,7 @@ void GpuHevcEncoder::fill_state(FrameSlot& sl, bool idr, int qp, int ref, int cu
     f.bl_safe_split = bl_safe_split_;
     f.depth_inter = common_.depth_inter();
     f.depth_intra = common_.depth_intra();
+    f.tskip = cfg_.hevc_transform_skip ? 1 : 0;
     f.aq = cfg_.aq;
     f.tu_split = cfg_.tu_split;  // 0 none, 1 8x8 nodes, 2 also 4x4 luma TUs
     f.chroma_qp_offset = cfg_.chroma_qp_offset;
@@ -300,7 +301,8 @@ void GpuHevcEncoder::enqueue_analysis_impl(bool idr, const uint8_t* src_y, const
     } else {
         h264::launch_hpel(geom_, sl.buf.me, hp_, hp_pitch_, stream_);
         h264::launch_me(geom_, sl.buf.me, src_y, stream_);
-        launch_hevc_inter(geom_, sl.buf, src_y, src_uv, stream_, cfg_.hevc_intra_in_p != 0);
+        launch_hevc_inter(geom_, sl.buf, src_y, src_uv, stream_, cfg_.hevc_intra_in_p != 0,
+                          cfg_.hevc_transform_skip != 0);
     }
     launch_hevc_layout(geom_, sl.buf, idr, common_.max_slices(), cfg_.hevc_slice_cost, cfg_.hevc_deblock(), sl.fs_host->sao != 0, src_y,
                        src_uv, stream_, cfg_.hevc_deblock_auto(), cfg_.hevc_intra_in_p != 0);

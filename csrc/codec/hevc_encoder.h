@@ -91,7 +91,7 @@ int intra_decide_mode(const uint8_t* sy, int pitch, int mb_w, int mb_h, int x, i
                       uint64_t safe, uint64_t safe_split = 0, bool split = false, int* tu4 = nullptr);
 // Direct vs bin-token CABAC on random slices (hevc_cpu.cpp); returns the slices checked.  intra_tu4:
 // intra units get 4x4 luma nodes too, under max_transform_hierarchy_depth_intra 2.
-int token_selftest(uint32_t seed, int slices, bool intra_tu4 = false);
+int token_selftest(uint32_t seed, int slices, bool intra_tu4 = false, bool tskip = false);
 // Entropy-code the slice of CTBs [first, end) with wavefront parallel processing (host): every CTB
 // row of the slice is a substream (fresh contexts in the slice's first row -- or when the picture
 // is one CTB wide -- else the contexts the row above had after its second CTB), written to `out` back to back;
@@ -111,6 +111,7 @@ class CpuHevcEncoder {
     const std::vector<uint8_t>& recon_uv() const { return rec_uv_[cur_]; }
     int coded_pitch() const { return cw_; }
     const std::vector<CuInfo>& cus() const { return cu_; }
+    bool tskip() const { return cfg_.hevc_transform_skip != 0; }
 
    private:
     void analyse_intra(const uint8_t* y, const uint8_t* uv, int pitch);
@@ -204,6 +205,7 @@ struct HevcFrameState {
     int32_t deblock_auto;  // EncoderConfig::deblock 2: k_hevc_db_auto decides deblock_on (h264_deblock.h rule)
     int32_t chroma_keep;   // EncoderConfig::hevc_chroma_keep: changing content keeps its chroma residual
     int32_t depth_intra;   // max_transform_hierarchy_depth_intra of the SPS (1: intra units may split, 2: 4x4 luma TUs)
+    int32_t tskip;         // EncoderConfig::hevc_transform_skip: every coded 4x4 TU sends transform_skip_flag
 };
 
 struct HevcOutHeader {
@@ -275,8 +277,9 @@ void launch_hevc_publish(const HevcDeviceBuffers& b, const HevcFrameState& fs, c
 // IDR + temporal AQ: the source luma into fs->save_src (pointer read on the device)
 void launch_hevc_save_src(const Geometry& g, const HevcDeviceBuffers& b, const uint8_t* src_y, hipStream_t s);
 // intra_p (EncoderConfig::hevc_intra_in_p): also leaves every unit's inter SATD in b.isatd
+// tskip (EncoderConfig::hevc_transform_skip): the split tree's 4x4 luma TUs may be transform-skipped
 void launch_hevc_inter(const Geometry& g, const HevcDeviceBuffers& b, const uint8_t* src_y, const uint8_t* src_uv,
-                       hipStream_t s, bool intra_p = false);
+                       hipStream_t s, bool intra_p = false, bool tskip = false);
 void launch_hevc_intra(const Geometry& g, const HevcDeviceBuffers& b, int slice_rows, int num_slices, int depth_intra,
                        const uint8_t* src_y, const uint8_t* src_uv, hipStream_t s);
 // Slice layout, per-slice decisions and (with deblock) the in-loop filter + final distortion:

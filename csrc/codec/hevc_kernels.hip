@@ -310,39 +310,80 @@ __device__ __forceinline__ SplitResult split_tus(TuBuf& t, const Mats& M, int qp
 // each (tu_encode_t<2> rules).  Levels to lv4 (node k TU j at 64k + 16j, scan order),
 // reconstruction to rec4 (16x16 luma, TuBuf layout); per-node SSE (node / display area) and bits
 // in the result.
+// kTs (EncoderConfig::hevc_transform_skip): every TU is also coded with transform_skip_flag 1
+// (tu4_skip_encode) and keeps that coding when choose_split prefers it over the TU's own samples, both
+// paying the flag's bit; lv4, rec4 and the per-node sums then hold the winners, and tskip the coded
+// skipped TUs (bit 4k + j).  The candidate rides in the same lanes between the same four phases (hevc_tu.h
+// Skip4): quantised while the row stage's results settle, trimmed beside the transformed levels,
+// reconstructed beside the inverse column stage, compared after the inverse rows.  No LDS stage, no
+// phase and no shuffle is added for it; the instance without it is the function as it always was.
 struct Split4Result {
     int node_sse[4], node_disp[4];
     uint32_t node_bits[4];
+    uint32_t tskip;
 };
+template <bool kTs>
 __device__ __forceinline__ Split4Result split4_luma(TuBuf& t, const Mats& M, int qp, bool valid, int16_t* lv4,
                                                     uint8_t* rec4, int x0, int y0, int disp_w, int disp_h) {
     const int lane = threadIdx.x & 63, j16 = lane >> 2;
     const int k = j16 >> 2, j = j16 & 3;
     const int tx = (k & 1) * 8 + (j & 1) * 4, ty = (k >> 1) * 8 + (j >> 1) * 4;  // TU origin in the CU
     const TuAt u = {ty * 16 + tx, 16, 16 * j16};
+    Skip4 sk = {};
     if (valid) tu_fwd_rows<2, 4>(t, M, u);
+    if (kTs && valid) tu4_skip_quant(t, u, qp, sk);
     wave_lds_sync();
     int ll[4] = {0, 0, 0, 0}, si[4] = {0, 0, 0, 0};
     if (valid) tu_fwd_cols_quant<2, 4>(t, M, u, qp, false, ll, si);
     tu_decimate_group<4>(ll, 2, false);
     tu_trim_group<4>(ll, si);
+    if (kTs) tu4_skip_trim(sk, si);
     int nz = 0, bl = 0;
     if (valid) tu_store_dequant<2, 4>(t, u, qp, ll, si, lv4 + u.buf, nz, bl);
     nz = gsum<4>(nz);
     bl = gsum<4>(bl);
     wave_lds_sync();
     if (valid) tu_inv_cols<2, 4>(t, M, u);
+    if (kTs && valid)
+        tu4_skip_rec(t, u, qp, sk, [&](int x) { return x0 + tx + x < disp_w && y0 + ty + (lane & 3) < disp_h; });
     wave_lds_sync();
     int sf = 0, sd = 0;
+    uint32_t rd = 0;  // kTs: the lane's transformed row, held back until the TU's coding is chosen
     if (valid)
         tu_inv_rows_rec<2, 4>(t, M, u, nz != 0, [&](int y, int x, int o, int v, int e2) {
             sf += e2;
             sd += (x0 + tx + x < disp_w && y0 + ty + y < disp_h) ? e2 : 0;
-            rec4[o] = (uint8_t)v;
+            if (kTs)
+                rd |= (uint32_t)v << (8 * x);
+            else
+                rec4[o] = (uint8_t)v;
         });
     Split4Result out;
+    out.tskip = 0;
+    int tb = 0;  // kTs: tu_bits_est of the TU's winner
+    if (kTs) {  // the TU's two codings: quad-uniform sums, one decision per quad
+        tb = nz ? bl + 4 : 1;
+        const int sse_d = quad_sum(sf), sse_s = quad_sum(sk.sse), tb_s = sk.nz ? sk.bits + 4 : 1;
+        const bool skip = valid && choose_split((uint64_t)sse_d, (uint32_t)tb + 1u, (uint64_t)sse_s, (uint32_t)tb_s + 1u, qp);
+        if (skip) {
+            sf = sk.sse;
+            sd = sk.disp;
+            tb = tb_s;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) lv4[u.buf + si[q]] = (int16_t)sk.l[q];
+        }
+        if (valid) {
+            const uint32_t row = skip ? sk.rec : rd;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) rec4[u.org + (lane & 3) * 16 + q] = (uint8_t)(row >> (8 * q));
+        }
+        // one ballot for the wave: a coded skipped TU sets the bit of its quad's first lane
+        const uint64_t b = __ballot(skip && sk.nz != 0 && (lane & 3) == 0);
+#pragma unroll
+        for (int q = 0; q < 16; ++q) out.tskip |= (uint32_t)((b >> (4 * q)) & 1u) << q;
+    }
     const int gs = gsum<16>(sf), gd = gsum<16>(sd);
-    const int gb = gsum<16>((lane & 3) == 0 ? (nz ? bl + 4 : 1) : 0);  // the node's four TUs
+    const int gb = gsum<16>((lane & 3) == 0 ? (kTs ? tb : (nz ? bl + 4 : 1)) : 0);  // the node's four TUs
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
         out.node_sse[q] = __builtin_amdgcn_readlane(gs, 16 * q);
@@ -401,8 +442,10 @@ __device__ __forceinline__ int satd16_wave(mf_h4 a, mf_h4 hm) {
 
 // ------------------------------------------------------------------ inter
 // kSatd (EncoderConfig::hevc_intra_in_p): the unit's luma SATD of source minus inter prediction goes
-// to isatd for k_hevc_intra_p_modes; the instance without it is the kernel as it always was
-template <bool kSatd>
+// to isatd for k_hevc_intra_p_modes; the instance without it is the kernel as it always was.
+// kTs (EncoderConfig::hevc_transform_skip): the 4x4 luma TUs of the split tree may be transform-skipped
+// (split4_luma<true>), CuInfo::tskip says which; again the instance without it is the kernel as it was
+template <bool kSatd, bool kTs>
 __global__ __launch_bounds__(256) void k_hevc_inter(Geometry g, const HevcFrameState* __restrict__ fs,
                                                      const h264::MbInfo* __restrict__ mbs,
                                                      const uint8_t* __restrict__ src_y,
@@ -553,15 +596,17 @@ __global__ __launch_bounds__(256) void k_hevc_inter(Geometry g, const HevcFrameS
         r2 = split_tus(t, M, qp, qpc, valid, lv2[wave], rec2[wave], x0, y0, g.width, g.height);
     // tu_split 2: every node whose 8x8 TU coded a level may become four 4x4 TUs (split_encode try4)
     int tu4 = 0;
+    uint32_t tskip = 0;  // (kTs) the skipped TUs of the nodes in tu4
     if (try_split && fs->tu_split >= 2 &&
         split_worth_trying(r2.node_lv[0] + r2.node_lv[1] + r2.node_lv[2] + r2.node_lv[3])) {  // wave-uniform
-        const Split4Result r4 = split4_luma(t, M, qp, valid, lv4[wave], rec4[wave], x0, y0, g.width, g.height);
+        const Split4Result r4 = split4_luma<kTs>(t, M, qp, valid, lv4[wave], rec4[wave], x0, y0, g.width, g.height);
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             if (!split_worth_trying(r2.node_lv[k])) continue;
             if (!choose_split((uint64_t)r2.node_sse[k], r2.node_bits[k], (uint64_t)r4.node_sse[k], r4.node_bits[k], qp))
                 continue;
             tu4 |= 1 << k;
+            if (kTs) tskip |= r4.tskip & (0xfu << (4 * k));
             r2.sse_full += r4.node_sse[k] - r2.node_sse[k];
             r2.sse_y_full += r4.node_sse[k] - r2.node_sse[k];
             r2.sse[0] += r4.node_disp[k] - r2.node_disp[k];
@@ -624,12 +669,14 @@ __global__ __launch_bounds__(256) void k_hevc_inter(Geometry g, const HevcFrameS
         if (fs->tu_split) {
             c.tu_split = split ? 2 : 1;
             if (split) ss.apply(c);
+            if (kTs && split) c.tskip = (uint16_t)tskip;
         }
         if (drop) {  // no residual left (chroma was dropped before coding): cu_summarise of zeros
             c.tu_split = fs->tu_split ? 1 : 0;
             c.cbf = c.cbf_y4 = c.cbf_c4 = 0;
             c.tu4 = 0;
             c.cbf_y16 = 0;
+            if (kTs) c.tskip = 0;
             c.last[0] = c.last[1] = c.last[2] = 0;
             c.csbf_y = 0;
             c.csbf_c[0] = c.csbf_c[1] = 0;
@@ -1921,7 +1968,8 @@ __global__ __launch_bounds__(64) void k_hevc_bins(Geometry g, const HevcFrameSta
     const int first = uni(slice_first[s]);
     const int end = s + 1 < ns ? uni(slice_first[s + 1]) : nctb;
     const UnitSyn u = unit_syn(CuGet{cus}, fs->sao ? sao : nullptr, x, y, g.mb_w, g.mb_h, fs->idr != 0, first, end,
-                               fs->wpp != 0, fs->depth_inter, fs->depth_intra, (int)uni((uint32_t)qp_pred[i]));
+                               fs->wpp != 0, fs->depth_inter, fs->depth_intra, (int)uni((uint32_t)qp_pred[i]),
+                               fs->tskip != 0);
     const CuInfo cu = load_cu(cus, i);
     const CoefArray cf{coef + (size_t)i * kCoefPerCu};
     // lane p binarises part p of the unit (coding order) into its LDS run
@@ -2842,14 +2890,12 @@ void launch_hevc_save_src(const Geometry& g, const HevcDeviceBuffers& b, const u
 }
 
 void launch_hevc_inter(const Geometry& g, const HevcDeviceBuffers& b, const uint8_t* src_y, const uint8_t* src_uv,
-                       hipStream_t s, bool intra_p) {
+                       hipStream_t s, bool intra_p, bool tskip) {
     const int nctb = ctb_cols(g.mb_w) * ctb_rows(g.mb_h);
-    if (intra_p)
-        hipLaunchKernelGGL(k_hevc_inter<true>, dim3(nctb), dim3(256), 0, s, g, b.fs, b.me.mb, src_y, src_uv, b.cu, b.coef,
-                           b.cost, b.qpc, b.isatd);
-    else
-        hipLaunchKernelGGL(k_hevc_inter<false>, dim3(nctb), dim3(256), 0, s, g, b.fs, b.me.mb, src_y, src_uv, b.cu, b.coef,
-                           b.cost, b.qpc, b.isatd);
+    auto* const kern = intra_p ? (tskip ? k_hevc_inter<true, true> : k_hevc_inter<true, false>)
+                               : (tskip ? k_hevc_inter<false, true> : k_hevc_inter<false, false>);
+    hipLaunchKernelGGL(kern, dim3(nctb), dim3(256), 0, s, g, b.fs, b.me.mb, src_y, src_uv, b.cu, b.coef, b.cost, b.qpc,
+                       b.isatd);
 }
 
 void launch_hevc_intra(const Geometry& g, const HevcDeviceBuffers& b, int slice_rows, int num_slices, int depth_intra,

@@ -130,35 +130,51 @@ __device__ __forceinline__ void tu_fwd_cols_quant(const TuBuf& t, const Mats& M,
         si[j] = scan_index(L, k, k2);
     }
 }
+// Group reductions of the two rules below.  kQuad (G == 4 only): the group is the lane's DPP quad, so
+// the reduction is four quad_perm moves on the VALU and stays off the LDS crossbar that the
+// xor-shuffle ladder of gsum / gmax goes through -- the transform-skip candidate reduces this way
+// while the transformed candidate's ds_read / v_dot2 stages own the LDS pipe.
+__device__ __forceinline__ int quad_max(int v) { return max(max(qbc<0>(v), qbc<1>(v)), max(qbc<2>(v), qbc<3>(v))); }
+template <int G, bool kQuad>
+__device__ __forceinline__ int tu_gsum(int v) {
+    if constexpr (kQuad) return quad_sum(v);
+    else return gsum<G>(v);
+}
+template <int G, bool kQuad>
+__device__ __forceinline__ int tu_gmax(int v) {
+    if constexpr (kQuad) return quad_max(v);
+    else return gmax<G>(v);
+}
 // Decimation of the TU on this lane's aligned group of G lanes (tu_decimate, group-uniform).
-template <int G, int N>
+template <int G, int N, bool kQuad = false>
 __device__ __forceinline__ void tu_decimate_group(int (&l)[N], int log2n, bool intra) {
+    static_assert(!kQuad || G == 4, "a quad is four lanes");
     int nz = 0, mx = 0;
     for (int j = 0; j < N; ++j) {
         nz += l[j] != 0;
         mx = max(mx, abs(l[j]));
     }
-    if (tu_decimate(log2n, intra, gsum<G>(nz), gmax<G>(mx)))
+    if (tu_decimate(log2n, intra, tu_gsum<G, kQuad>(nz), tu_gmax<G, kQuad>(mx)))
         for (int j = 0; j < N; ++j) l[j] = 0;
 }
 // Trailing isolated +-1 trim of the TU on this lane's group (tu_encode_t rule): the lane owning
 // the last level clears it; a stopped TU stays stopped, and the loop ends once every TU of the
 // wave has stopped.  Called by the whole wave.
-template <int G, int N>
+template <int G, int N, bool kQuad = false>
 __device__ __forceinline__ void tu_trim_group(int (&l)[N], const int (&si)[N]) {
     bool on = true;
     for (int it = 0; it < kTrimIters; ++it) {
         int last = -1;
         for (int j = 0; j < N; ++j)
             if (l[j]) last = max(last, si[j]);
-        last = gmax<G>(last);
+        last = tu_gmax<G, kQuad>(last);
         int prev = -1, lv = 0;
         for (int j = 0; j < N; ++j) {
             if (l[j] && si[j] < last) prev = max(prev, si[j]);
             if (l[j] && si[j] == last) lv = abs(l[j]);
         }
-        prev = gmax<G>(prev);
-        lv = gmax<G>(lv);
+        prev = tu_gmax<G, kQuad>(prev);
+        lv = tu_gmax<G, kQuad>(lv);
         if (last < 0 || lv != 1 || last - prev <= kTrimGap) on = false;
         if (!__any(on)) break;
         if (on)
@@ -207,6 +223,63 @@ __device__ __forceinline__ void tu_inv_rows_rec(const TuBuf& t, const Mats& M, T
         const int o = u.org + y * u.pitch + x, p = t.pred[o];
         const int v = clip255(p + r), e = p + t.res[o] - v;
         emit(y, x, o, v, e * e);
+    }
+}
+
+// ---- the transform-skip candidate of a 4x4 luma TU (tu4_skip_encode of hevc_core.h), on the lanes
+// of the <2, 4> stages: four lanes per TU, lane q of the quad owns row q -- coefficients (q, 0..3) in
+// the transformed candidate, samples (q, 0..3) here, so both candidates' levels sit at the same scan
+// positions si[] of the same lane.  The candidate has no matrix and no stage buffer: one 8-byte read
+// of the lane's residual row, one 4-byte read of its prediction row, everything else in registers
+// and quad DPP.  Its steps carry no LDS dependence on the transformed candidate's stages, so the
+// caller places them between those stages' wave_lds_sync() phases, where they fill the ds_read_b128 /
+// v_dot2 latency.
+struct Skip4 {
+    int l[4];       // levels of samples (q, 0..3)
+    uint32_t rec;   // the row's reconstructed samples, one byte each
+    int sse, disp;  // squared error of the row: whole / inside the display area
+    int nz, bits;   // the TU's coded levels and their level_bits (quad-uniform)
+};
+__device__ __forceinline__ uint2 tu4_row_res(const TuBuf& t, TuAt u) {
+    return *reinterpret_cast<const uint2*>(t.res + u.org + (int)(threadIdx.x & 3) * u.pitch);
+}
+__device__ __forceinline__ int tu4_row_sample(uint2 w, int j) {
+    return (int)(int16_t)(((j & 2) ? w.y : w.x) >> ((j & 1) * 16));
+}
+// forward "transform" + quantisation
+__device__ __forceinline__ void tu4_skip_quant(const TuBuf& t, TuAt u, int qp, Skip4& s) {
+    const uint2 w = tu4_row_res(t, u);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) s.l[j] = quant_coef(tskip_fwd(tu4_row_sample(w, j)), qp, 2, false);
+}
+// decimation and trailing trim on the quad; si: the lane's scan positions (tu_fwd_cols_quant<2, 4>)
+__device__ __forceinline__ void tu4_skip_trim(Skip4& s, const int (&si)[4]) {
+    tu_decimate_group<4, 4, true>(s.l, 2, false);
+    tu_trim_group<4, 4, true>(s.l, si);
+    int nz = 0, b = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        nz += s.l[j] != 0;
+        b += level_bits(s.l[j]);
+    }
+    s.nz = quad_sum(nz);
+    s.bits = quad_sum(b);
+}
+// dequantisation + reconstruction of the lane's row; in_disp(x): column x of the TU is displayed
+template <class InDisp>
+__device__ __forceinline__ void tu4_skip_rec(const TuBuf& t, TuAt u, int qp, Skip4& s, InDisp in_disp) {
+    const uint2 w = tu4_row_res(t, u);
+    const uint32_t pw = *reinterpret_cast<const uint32_t*>(t.pred + u.org + (int)(threadIdx.x & 3) * u.pitch);
+    s.rec = 0;
+    s.sse = s.disp = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int p = (int)((pw >> (8 * j)) & 0xffu);
+        const int v = clip255(p + tskip_inv(dequant_coef(s.l[j], qp, 2)));
+        const int e = p + tu4_row_sample(w, j) - v;
+        s.rec |= (uint32_t)v << (8 * j);
+        s.sse += e * e;
+        s.disp += in_disp(j) ? e * e : 0;
     }
 }
 

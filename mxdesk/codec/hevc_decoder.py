@@ -11,7 +11,7 @@ no code with this file.
 Supported: VPS/SPS/PPS (incl. VUI), I and P slices (one reference picture, short-term RPS
 from the SPS), coding quadtrees with split_cu_flag, PartMode 2Nx2N (intra and inter),
 transform trees with split_transform_flag, residual coding for 4x4..32x32 TUs (scanIdx
-0/1/2, no sign hiding, no transform skip), cu_qp_delta, conformance window cropping.
+0/1/2, no sign hiding; transform skip of 4x4 TUs), cu_qp_delta, conformance window cropping.
 Both in-loop filters are implemented: deblocking (8.7.2) and sample adaptive offset (8.7.3,
 band and edge offsets with CTB merge-left/up, 7.3.8.3).  TMVP must be off (mxdesk's encoder
 guarantees it); anything else raises ``NotImplementedError``.  Slow; meant for small test pictures.
@@ -90,6 +90,7 @@ _INIT = {
                                       [107, 167, 91, 107, 107, 167]),
     "sao_merge_flag": ([153], [153], [153]),       # sao_merge_left_flag and sao_merge_up_flag share it
     "sao_type_idx": ([200], [185], [160]),          # first bin of sao_type_idx_luma / _chroma
+    "transform_skip_flag": ([139, 139], [139, 139], [139, 139]),  # Table 9-26: luma, chroma
 }
 _INIT["last_sig_coeff_y_prefix"] = _INIT["last_sig_coeff_x_prefix"]
 
@@ -589,6 +590,7 @@ class Decoder:
         self.cur: Picture | None = None
         self.prev_poc_tid0 = 0
         self.stats = {"skip": 0, "merge": 0, "amvp": 0, "intra": 0, "slices": 0}
+        self.ts_flag = 0  # transform_skip_flag of the TU parsed last (_residual)
 
     # ---------------------------------------------------------------- top level
     def decode(self, stream: bytes) -> list[tuple[np.ndarray, np.ndarray, np.ndarray]]:
@@ -1324,12 +1326,19 @@ class Decoder:
 
     def _add_residual(self, plane, x0, y0, n, levels, qp, log2, dst=False):
         """Scaling (8.6.2/8.6.3) and the inverse transform (8.6.4.2): the DCT-like core transform,
-        or for a 4x4 intra luma TU the DST-VII matrix (8.6.4.2 trType 1)."""
+        or for a 4x4 intra luma TU the DST-VII matrix (8.6.4.2 trType 1).  A TU with transform_skip_flag
+        (ts_flag, left by the _residual call that parsed these levels) has no transform of either kind (no DST for an intra 4x4 luma TU): its residual is the scaled
+        level shifted left by tsShift = 7, then rounded by bdShift = 20 - BitDepth like any other."""
         if levels is None:
             return
         d = (levels.astype(np.int64) * 16 * _LEVEL_SCALE[qp % 6]) << (qp // 6)
         bd = 8 + log2 - 5
         d = np.clip((d + (1 << (bd - 1))) >> bd, -32768, 32767)
+        if self.ts_flag:
+            self.stats["transform_skip"] = self.stats.get("transform_skip", 0) + 1
+            r = ((d << 7) + 2048) >> 12
+            plane[y0:y0 + n, x0:x0 + n] = np.clip(plane[y0:y0 + n, x0:x0 + n] + r, 0, 255)
+            return
         t = _DST4 if dst else _tmat(n)
         # d is indexed [y][x] (row = vertical frequency); columns first, then rows
         e = t.T @ d
@@ -1340,6 +1349,13 @@ class Decoder:
     # ---------------------------------------------------------------- residual_coding (7.3.8.11)
     def _residual(self, cab: Cabac, log2: int, cidx: int, intra_mode):
         n = 1 << log2
+        # transform_skip_flag: 4x4 TUs (Log2MaxTransformSkipSize 2 without the range extensions) of every
+        # component while the PPS enables it; the TU's reconstruction reads it from ts_flag
+        self.ts_flag = 0
+        if log2 == 2 and cidx == 0:
+            self.stats["luma4_coded"] = self.stats.get("luma4_coded", 0) + 1
+        if self.pps.transform_skip and log2 <= 2:
+            self.ts_flag = cab.decision("transform_skip_flag", 1 if cidx else 0)
         scan_idx = 0
         if intra_mode is not None and (log2 == 2 or (log2 == 3 and cidx == 0)):
             if 6 <= intra_mode <= 14:

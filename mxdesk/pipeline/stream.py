@@ -211,6 +211,8 @@ def apply_encoder_args(enc, a: dict) -> None:
         enc.hevc_intra_split = a["hevc_intra_split"]
     if "hevc_intra_in_p" in a:  # HEVC P pictures: intra units (EncoderConfig::hevc_intra_in_p)
         enc.hevc_intra_in_p = a["hevc_intra_in_p"]
+    if "hevc_transform_skip" in a:  # HEVC P pictures: transform skip (EncoderConfig::hevc_transform_skip)
+        enc.hevc_transform_skip = a["hevc_transform_skip"]
     if "vp8_tokens" in a:  # VP8 token partitions coded on the host or the GPU (EncoderConfig::vp8_tokens)
         enc.vp8_tokens = 1 if a["vp8_tokens"] == "gpu" else 0
 
@@ -222,7 +224,8 @@ class StreamPipeline:
                  capture: Any = None, metrics: SessionMetrics | None = None, queue_frames: int | None = None,
                  stall_s: float = 2.0, paced: bool = True, codec: str = "h264",
                  idr_min_interval_s: float | None = None, scroll_range: int = 0, partitions: int = 1,
-                 hevc_intra_split: int = 1, vp8_tokens: str = "host", hevc_intra_in_p: int = 0):
+                 hevc_intra_split: int = 1, vp8_tokens: str = "host", hevc_intra_in_p: int = 0,
+                 hevc_transform_skip: int = 0):
         if codec not in CODEC_IDS:
             raise ValueError(f"unknown codec {codec!r} (h264 | hevc | vp8)")
         self.codec = codec
@@ -243,7 +246,7 @@ class StreamPipeline:
         self._enc_args = dict(bitrate_kbps=bitrate_kbps, keyint=keyint, search_range=search_range, subpel=subpel,
                               noise=noise, scroll_range=scroll_range, partitions=partitions,
                               hevc_intra_split=hevc_intra_split, vp8_tokens=vp8_tokens,
-                              hevc_intra_in_p=hevc_intra_in_p)
+                              hevc_intra_in_p=hevc_intra_in_p, hevc_transform_skip=hevc_transform_skip)
         self.last_scroll = (0, 0)  # scroll hint of the last P picture (H.264 with scroll_range; /status)
         self._subs: list[_Subscriber] = []
         self._lock = threading.Lock()

@@ -161,6 +161,9 @@ SCHEMA: list[Var] = [
     Var("hevc_intra_in_p", ["MXDESK_HEVC_INTRA_IN_P"], 0, int,
         "HEVC P pictures: 1 = a 16x16 unit may be coded intra from the reconstruction around it where that beats "
         "its motion-compensated prediction, 0 = every unit is inter"),
+    Var("hevc_transform_skip", ["MXDESK_HEVC_TRANSFORM_SKIP"], 0, int,
+        "HEVC P pictures: 1 = a 4x4 luma TU of the inter transform tree may be coded with transform_skip_flag "
+        "(one-sample strokes of text and outlines), 0 = every TU is transformed"),
     Var("vp8_tokens", ["MXDESK_VP8_TOKENS"], "host", str,
         "VP8 token partitions boolean-coded by: host (writer threads) | gpu (k_vp8_tokens; same stream)"),
     Var("subpel", ["MXDESK_SUBPEL"], True, bool, "quarter-pel motion refinement"),
@@ -279,6 +282,8 @@ class Config:
             raise ValueError("MXDESK_HEVC_INTRA_SPLIT must be 0, 1 or 2")
         if v["hevc_intra_in_p"] not in (0, 1):
             raise ValueError("MXDESK_HEVC_INTRA_IN_P must be 0 or 1")
+        if v["hevc_transform_skip"] not in (0, 1):
+            raise ValueError("MXDESK_HEVC_TRANSFORM_SKIP must be 0 or 1")
         if v["vp8_tokens"] not in ("host", "gpu"):
             raise ValueError("MXDESK_VP8_TOKENS must be host or gpu")
         if v["source"] not in ("auto", "synthetic", "x11"):
