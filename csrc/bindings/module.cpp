@@ -90,6 +90,8 @@ PYBIND11_MODULE(_native, m) {
         if (hipGetDeviceCount(&n) != hipSuccess) return 0;
         return n;
     });
+    m.def("gpu_live_handles", &GpuArena::live,
+          "HIP handles (memory, events, streams, page-locked ranges) the process's native objects hold now");
     m.def("set_device", [](int d) { HIP_CHECK(hipSetDevice(d)); });
     m.def("device_name", [](int d) {
         hipDeviceProp_t p;
@@ -709,7 +711,7 @@ PYBIND11_MODULE(_native, m) {
                                  as_ptr<const float>(wx),
                                  as_ptr<const int>(y0),
                                  as_ptr<const float>(wy)};
-            void* frags = nullptr;
+            GpuArena frags;
             if (mfma) {  // test path: tables back to the host, fragments built and uploaded per call
                 std::vector<int> hx0(out_w), hy0(out_h);
                 std::vector<float> hwx((size_t)out_w * taps_x), hwy((size_t)out_h * taps_y);
@@ -720,17 +722,14 @@ PYBIND11_MODULE(_native, m) {
                 pix::ScaleFragsHost fr;
                 if (!pix::build_scale_frags(in_w, in_h, out_w, out_h, cw, ch, hx0, hwx, taps_x, hy0, hwy, taps_y, fr))
                     throw std::invalid_argument("scale_to_nv12: scale factor outside the MFMA kernel's range");
-                pix::upload_scale_frags(fr, &frags, t.mf);
+                pix::upload_scale_frags(fr, frags, t.mf);
                 t.mf.force_strip = strip;  // else the one-tile-per-workgroup MFMA kernel
             }
             const pix::ScaleForm form =
                 pix::launch_scale_to_nv12(as_ptr<const uint8_t>(in), in_pitch, in_w, in_h, t, as_ptr<uint8_t>(y),
                                           as_ptr<uint8_t>(uv), out_pitch, cw, ch, as_stream(stream));
             HIP_CHECK(hipGetLastError());
-            if (frags) {
-                HIP_CHECK(hipStreamSynchronize(as_stream(stream)));
-                HIP_CHECK(hipFree(frags));
-            }
+            if (mfma) HIP_CHECK(hipStreamSynchronize(as_stream(stream)));  // the kernel reads the fragments
             return std::string(pix::scale_form_name(form));  // "valu", "tile" or "strip": the kernel that ran
         },
         py::arg("in_ptr"), py::arg("in_pitch"), py::arg("in_w"), py::arg("in_h"), py::arg("out_w"), py::arg("out_h"),
@@ -791,33 +790,20 @@ PYBIND11_MODULE(_native, m) {
             // k_sse_masked with scratch allocated as Session does (partials, a counter zeroed once,
             // a mapped host word), launched `repeat` times on the same scratch: one total per launch
             if (w < 1 || h < 1 || repeat < 1) throw std::invalid_argument("sse_masked: bad geometry");
-            unsigned long long* part = nullptr;
-            unsigned int* counter = nullptr;
-            unsigned long long* host = nullptr;
+            GpuArena res;
             std::vector<unsigned long long> totals;
-            auto release = [&] {
-                if (part) (void)hipFree(part);
-                if (counter) (void)hipFree(counter);
-                if (host) (void)hipHostFree(host);
-            };
-            try {
-                HIP_CHECK(hipMalloc(&part, (size_t)pix::sse_masked_blocks(w, h) * sizeof(unsigned long long)));
-                HIP_CHECK(hipMalloc(&counter, sizeof(unsigned int)));
-                HIP_CHECK(hipMemset(counter, 0, sizeof(unsigned int)));
-                HIP_CHECK(hipHostMalloc(&host, sizeof(unsigned long long), hipHostMallocMapped));
-                for (int i = 0; i < repeat; ++i) {
-                    *host = ~0ull;
-                    pix::launch_sse_masked(as_ptr<const uint8_t>(a), as_ptr<const uint8_t>(b), pitch, w, h, mx0, my0,
-                                           mx1, my1, part, counter, host, as_stream(stream));
-                    HIP_CHECK(hipGetLastError());
-                    HIP_CHECK(hipStreamSynchronize(as_stream(stream)));
-                    totals.push_back(*host);
-                }
-            } catch (...) {
-                release();
-                throw;
+            unsigned long long* part = res.device<unsigned long long>(pix::sse_masked_blocks(w, h));
+            unsigned int* counter = res.device<unsigned int>(1);
+            HIP_CHECK(hipMemset(counter, 0, sizeof(unsigned int)));
+            unsigned long long* host = res.pinned<unsigned long long>(1, hipHostMallocMapped);
+            for (int i = 0; i < repeat; ++i) {
+                *host = ~0ull;
+                pix::launch_sse_masked(as_ptr<const uint8_t>(a), as_ptr<const uint8_t>(b), pitch, w, h, mx0, my0, mx1,
+                                       my1, part, counter, host, as_stream(stream));
+                HIP_CHECK(hipGetLastError());
+                HIP_CHECK(hipStreamSynchronize(as_stream(stream)));
+                totals.push_back(*host);
             }
-            release();
             return totals;
         },
         py::arg("a_ptr"), py::arg("b_ptr"), py::arg("pitch"), py::arg("width"), py::arg("height"), py::arg("mx0"),

@@ -2,8 +2,6 @@
 // the CPU encoder.  See h264_gpu.h for the kernel chain.
 #include "h264_encoder.h"
 
-#include <hip/hip_ext.h>
-
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -211,29 +209,24 @@ std::vector<std::vector<uint8_t>> hpel_planes_for_test(const uint8_t* ref, int c
     g.pitch = pitch;
     const int hp_pitch = (coded_w + 2 * kHpelPad + 255) & ~255;
     const size_t hp_bytes = (size_t)hp_pitch * (coded_h + 2 * kHpelPad);
-    uint8_t* dref = nullptr;
+    GpuArena res;
     uint8_t* planes[4];
     FrameState fs{};
     DeviceBuffers b{};
-    HIP_CHECK(hipMalloc(&dref, (size_t)pitch * coded_h));
+    uint8_t* dref = res.device<uint8_t>((size_t)pitch * coded_h);
     HIP_CHECK(hipMemcpy(dref, ref, (size_t)pitch * coded_h, hipMemcpyHostToDevice));
     for (auto& p : planes) {
-        HIP_CHECK(hipMalloc(&p, hp_bytes));
+        p = res.device<uint8_t>(hp_bytes);
         HIP_CHECK(hipMemset(p, 0, hp_bytes));
     }
     fs.ref_y = dref;
-    HIP_CHECK(hipMalloc(&b.fs, sizeof(FrameState)));
+    b.fs = res.device<FrameState>(1);
     HIP_CHECK(hipMemcpy(b.fs, &fs, sizeof(FrameState), hipMemcpyHostToDevice));
     launch_hpel(g, b, planes, hp_pitch, nullptr);
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipDeviceSynchronize());
     std::vector<std::vector<uint8_t>> out(4, std::vector<uint8_t>(hp_bytes));
-    for (int i = 0; i < 4; ++i) {
-        HIP_CHECK(hipMemcpy(out[i].data(), planes[i], hp_bytes, hipMemcpyDeviceToHost));
-        (void)hipFree(planes[i]);
-    }
-    (void)hipFree(dref);
-    (void)hipFree(b.fs);
+    for (int i = 0; i < 4; ++i) HIP_CHECK(hipMemcpy(out[i].data(), planes[i], hp_bytes, hipMemcpyDeviceToHost));
     *hp_pitch_out = hp_pitch;
     return out;
 }
@@ -245,16 +238,13 @@ void mc_luma_for_test(const uint8_t* ref, int coded_w, int coded_h, int pitch, i
     g.mb_w = coded_w / 16;
     g.mb_h = coded_h / 16;
     g.pitch = pitch;
-    uint8_t *dref = nullptr, *dout = nullptr;
-    HIP_CHECK(hipMalloc(&dref, (size_t)pitch * coded_h));
-    HIP_CHECK(hipMalloc(&dout, 256));
+    GpuArena res;
+    uint8_t* dref = res.device<uint8_t>((size_t)pitch * coded_h);
+    uint8_t* dout = res.device<uint8_t>(256);
     HIP_CHECK(hipMemcpy(dref, ref, (size_t)pitch * coded_h, hipMemcpyHostToDevice));
     launch_mc_luma_test(g, dref, x4, y4, dout, nullptr);
-    const hipError_t e = hipGetLastError();
-    if (e == hipSuccess) (void)hipMemcpy(out, dout, 256, hipMemcpyDeviceToHost);
-    (void)hipFree(dref);
-    (void)hipFree(dout);
-    HIP_CHECK(e);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemcpy(out, dout, 256, hipMemcpyDeviceToHost));
 }
 
 // ------------------------------------------------------------------ GpuH264Encoder
@@ -267,67 +257,45 @@ constexpr unsigned kDeviceEvent = hipEventDisableTiming | hipEventReleaseToDevic
 void GpuH264Encoder::alloc_slot(FrameSlot& sl) {
     const int nmb = geom_.mb_w * geom_.mb_h;
     DeviceBuffers& b = sl.buf;
-    HIP_CHECK(hipMalloc(&b.fs, sizeof(FrameState)));
-    HIP_CHECK(hipMalloc(&b.mb, sizeof(MbInfo) * nmb));
-    HIP_CHECK(hipMemsetAsync(b.mb, 0, sizeof(MbInfo) * nmb, stream_));
-    HIP_CHECK(hipMalloc(&b.coef, sizeof(int16_t) * kCoefStride * nmb));
-    HIP_CHECK(hipMalloc(&b.slot, sizeof(uint32_t) * kSlotWords * (size_t)nmb));
-    HIP_CHECK(hipMalloc(&b.slot_bits, sizeof(uint32_t) * nmb));
-    HIP_CHECK(hipMalloc(&b.row_agg, sizeof(uint4) * (size_t)geom_.mb_h));
-    HIP_CHECK(hipMalloc(&b.row_sse, sizeof(unsigned long long) * 4 * 512));
-    HIP_CHECK(hipMalloc(&b.coded_info, sizeof(uint4) * nmb));
-    HIP_CHECK(hipMalloc(&b.slice_info, sizeof(uint32_t) * kSliceInfo * kMaxSlices));
-    HIP_CHECK(hipMemsetAsync(b.slice_info, 0, sizeof(uint32_t) * kSliceInfo * kMaxSlices, stream_));
+    GpuArena& r = sl.res;
+    b.fs = r.device<FrameState>(1);
+    b.mb = r.device_fill<MbInfo>(nmb, 0, stream_);
+    b.coef = r.device<int16_t>((size_t)kCoefStride * nmb);
+    b.slot = r.device<uint32_t>(kSlotWords * (size_t)nmb);
+    b.slot_bits = r.device<uint32_t>(nmb);
+    b.row_agg = r.device<uint4>(geom_.mb_h);
+    b.row_sse = r.device<unsigned long long>(4 * 512);
+    b.coded_info = r.device<uint4>(nmb);
+    b.slice_info = r.device_fill<uint32_t>(kSliceInfo * kMaxSlices, 0, stream_);
     // payload capacity: 768 B per MB (intra at low QP stays far below)
     b.out_bytes = (size_t)nmb * 768;
-    HIP_CHECK(hipMalloc(&b.quad_unit, sizeof(uint32_t) * (b.out_bytes / 16 + 1)));
-    HIP_CHECK(hipMalloc(&b.out_hdr, sizeof(OutHeader)));
-    HIP_CHECK(hipMalloc(&b.sse_part, 4 * sizeof(unsigned long long) * kSsePartStride));
-    HIP_CHECK(hipMalloc(&b.wave_prog, sizeof(int) * 4));
-    HIP_CHECK(hipMalloc(&b.mb_sse, sizeof(uint32_t) * 3 * (size_t)nmb));
-    HIP_CHECK(hipMalloc(&b.intra_gain, sizeof(int32_t) * (size_t)nmb));
-    HIP_CHECK(hipMalloc(&b.intra_cand, sizeof(int) * (size_t)nmb));
-    HIP_CHECK(hipMalloc(&b.db_rec, sizeof(uint4) * (size_t)nmb));
-    HIP_CHECK(hipMalloc(&b.db_rowq, sizeof(int) * (size_t)geom_.mb_h));
-    HIP_CHECK(hipMalloc(&b.db_glb, sizeof(uint64_t) * 2 * 24 * (size_t)nmb));
-    HIP_CHECK(hipMemsetAsync(b.db_glb, 0, sizeof(uint64_t) * 2 * 24 * (size_t)nmb, stream_));  // tag 0: no frame
-    HIP_CHECK(hipMalloc(&b.pack_done, sizeof(uint32_t)));
-    HIP_CHECK(hipMemsetAsync(b.pack_done, 0, sizeof(uint32_t), stream_));
-    HIP_CHECK(hipMalloc(&b.db_cnt, sizeof(uint32_t) * 4));
-    HIP_CHECK(hipMemsetAsync(b.db_cnt, 0, sizeof(uint32_t) * 4, stream_));
+    b.quad_unit = r.device<uint32_t>(b.out_bytes / 16 + 1);
+    b.out_hdr = r.device<OutHeader>(1);
+    b.sse_part = r.device<unsigned long long>(4 * (size_t)kSsePartStride);
+    b.wave_prog = r.device<int>(4);
+    b.mb_sse = r.device<uint32_t>(3 * (size_t)nmb);
+    b.intra_gain = r.device<int32_t>(nmb);
+    b.intra_cand = r.device<int>(nmb);
+    b.db_rec = r.device<uint4>(nmb);
+    b.db_rowq = r.device<int>(geom_.mb_h);
+    b.db_glb = r.device_fill<uint64_t>(2 * 24 * (size_t)nmb, 0, stream_);  // tag 0: no frame
+    b.pack_done = r.device_fill<uint32_t>(1, 0, stream_);
+    b.db_cnt = r.device_fill<uint32_t>(4, 0, stream_);
     if (const int D = scroll_reach(cfg_.scroll_range)) {  // vote histogram, hint
-        const size_t hist_bytes = sizeof(uint32_t) * (size_t)scroll_bins(D);
         sl.scroll.reach = D;
-        HIP_CHECK(hipMalloc(&sl.scroll.hist, hist_bytes));
-        HIP_CHECK(hipMemsetAsync(sl.scroll.hist, 0, hist_bytes, stream_));
-        HIP_CHECK(hipMalloc(&sl.scroll.hint, sizeof(int32_t) * 2));
-        HIP_CHECK(hipMemsetAsync(sl.scroll.hint, 0, sizeof(int32_t) * 2, stream_));
+        sl.scroll.hist = r.device_fill<uint32_t>(scroll_bins(D), 0, stream_);
+        sl.scroll.hint = r.device_fill<int32_t>(2, 0, stream_);
     }
-    HIP_CHECK(hipHostMalloc(&b.db_err, sizeof(int), hipHostMallocMapped));
+    b.db_err = r.pinned<int>(1, hipHostMallocMapped);
     *b.db_err = 0;
-    HIP_CHECK(hipHostMalloc(&sl.fs_host, sizeof(FrameState), hipHostMallocDefault));
-    HIP_CHECK(hipHostMalloc(&sl.host_out, kOutPayloadOffset + b.out_bytes + 16, hipHostMallocMapped));
+    sl.fs_host = r.pinned<FrameState>(1, hipHostMallocDefault);
+    sl.host_out = r.pinned<uint8_t>(kOutPayloadOffset + b.out_bytes + 16, hipHostMallocMapped);
     std::memset(sl.host_out, 0, kOutPayloadOffset);
-    HIP_CHECK(hipEventCreateWithFlags(&sl.start, hipEventDisableTiming));
-    HIP_CHECK(hipEventCreateWithFlags(&sl.analysis_done, kDeviceEvent));
-    HIP_CHECK(hipEventCreateWithFlags(&sl.deblock_done, kDeviceEvent));
-    HIP_CHECK(hipEventCreateWithFlags(&sl.me_done, kDeviceEvent));
-    HIP_CHECK(hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
-}
-
-void GpuH264Encoder::free_slot(FrameSlot& sl) {
-    DeviceBuffers& b = sl.buf;
-    for (void* p : {(void*)b.fs, (void*)b.mb, (void*)b.coef, (void*)b.slot, (void*)b.slot_bits, (void*)b.row_agg,
-                    (void*)b.row_sse, (void*)b.coded_info, (void*)b.slice_info,
-                    (void*)b.out_hdr, (void*)b.sse_part, (void*)b.wave_prog, (void*)b.mb_sse, (void*)b.intra_gain, (void*)b.intra_cand, (void*)b.quad_unit,
-                    (void*)b.db_rec, (void*)b.db_rowq, (void*)b.db_glb, (void*)b.pack_done, (void*)b.db_cnt,
-                    (void*)sl.scroll.hist, (void*)sl.scroll.hint})
-        if (p) (void)hipFree(p);
-    if (b.db_err) (void)hipHostFree(b.db_err);
-    if (sl.fs_host) (void)hipHostFree(sl.fs_host);
-    if (sl.host_out) (void)hipHostFree(sl.host_out);
-    for (hipEvent_t e : {sl.start, sl.analysis_done, sl.deblock_done, sl.done, sl.me_done})
-        if (e) (void)hipEventDestroy(e);
+    sl.start = r.event(hipEventDisableTiming);
+    sl.analysis_done = r.event(kDeviceEvent);
+    sl.deblock_done = r.event(kDeviceEvent);
+    sl.me_done = r.event(kDeviceEvent);
+    sl.done = r.event(hipEventDisableTiming);
 }
 
 GpuH264Encoder::GpuH264Encoder(const EncoderConfig& cfg, hipStream_t stream)
@@ -336,44 +304,25 @@ GpuH264Encoder::GpuH264Encoder(const EncoderConfig& cfg, hipStream_t stream)
         throw std::invalid_argument("pipeline_depth must be 1 to 4");
     depth_ = cfg.pipeline_depth;
     db_lag_.reset(cfg_.h264_deblock_mode());
-    geom_.width = cfg.width;
-    geom_.height = cfg.height;
-    geom_.mb_w = common_.mb_w();
-    geom_.mb_h = common_.mb_h();
-    geom_.coded_w = geom_.mb_w * 16;
-    geom_.coded_h = geom_.mb_h * 16;
-    geom_.pitch = (geom_.coded_w + 255) & ~255;
+    geom_ = make_geometry(cfg.width, cfg.height, common_.mb_w(), common_.mb_h());
     if (geom_.mb_h > kMaxSlices) throw std::invalid_argument("picture too tall");
     if (geom_.mb_w > 512) throw std::invalid_argument("picture too wide (k_intra_wave stages <= 512 MBs per row)");
     if (geom_.mb_h > kSsePartStride)
         throw std::invalid_argument("frame too large for the distortion partials");
     const size_t ysz = (size_t)geom_.pitch * geom_.coded_h, uvsz = ysz / 2;
     for (int i = 0; i < 2; ++i) {
-        HIP_CHECK(hipMalloc(&rec_y_[i], ysz));
-        HIP_CHECK(hipMalloc(&rec_uv_[i], uvsz));
-        HIP_CHECK(hipMemsetAsync(rec_y_[i], 16, ysz, stream_));
-        HIP_CHECK(hipMemsetAsync(rec_uv_[i], 128, uvsz, stream_));
-        HIP_CHECK(hipMalloc(&src_keep_[i], ysz));
-        HIP_CHECK(hipMemsetAsync(src_keep_[i], 16, ysz, stream_));
+        rec_y_[i] = res_.device_fill<uint8_t>(ysz, 16, stream_);
+        rec_uv_[i] = res_.device_fill<uint8_t>(uvsz, 128, stream_);
+        src_keep_[i] = res_.device_fill<uint8_t>(ysz, 16, stream_);
     }
-    if (cfg.mask_x1 > cfg.mask_x0 && cfg.mask_y1 > cfg.mask_y0) {
-        mask_mb_[0] = std::max(0, cfg.mask_x0) / 16;
-        mask_mb_[1] = std::max(0, cfg.mask_y0) / 16;
-        mask_mb_[2] = std::min(geom_.mb_w, (cfg.mask_x1 + 15) / 16);
-        mask_mb_[3] = std::min(geom_.mb_h, (cfg.mask_y1 + 15) / 16);
-    }
-    masked_pixels_ = (int64_t)cfg.width * cfg.height;
-    for (int my = mask_mb_[1]; my < mask_mb_[3]; ++my)
-        for (int mx = mask_mb_[0]; mx < mask_mb_[2]; ++mx)
-            masked_pixels_ -= (int64_t)std::max(0, std::min(16, cfg.width - 16 * mx)) *
-                              std::max(0, std::min(16, cfg.height - 16 * my));
-    if (cfg_.h264_deblock()) HIP_CHECK(hipMalloc(&rec_unf_, ysz));
+    masked_pixels_ = mask_units(geom_, cfg.mask_x0, cfg.mask_y0, cfg.mask_x1, cfg.mask_y1, mask_mb_);
+    if (cfg_.h264_deblock()) rec_unf_ = res_.device<uint8_t>(ysz);
     for (int i = 0; i < depth_; ++i) alloc_slot(slots_[i]);
     clock_khz_ = device_clock_khz();
     if (depth_ > 1) {
-        HIP_CHECK(hipStreamCreateWithFlags(&stream_e_, hipStreamNonBlocking));
+        stream_e_ = res_.stream(hipStreamNonBlocking);
         if (cfg_.h264_deblock()) {
-            HIP_CHECK(hipEventCreateWithFlags(&ev_hpu_, kDeviceEvent));
+            ev_hpu_ = res_.event(kDeviceEvent);
             HIP_CHECK(hipEventRecord(ev_hpu_, stream_));
         }
     }
@@ -391,7 +340,7 @@ void GpuH264Encoder::ensure_me_stream() {
     if (stream_e2_) {  // its hardware queue goes to the side search: the chains already queued finish first
         drain_launcher();
         HIP_CHECK(hipStreamSynchronize(stream_e2_));
-        HIP_CHECK(hipStreamDestroy(stream_e2_));
+        res_.release(stream_e2_);
         stream_e2_ = nullptr;
     }
     // The side-stream search may keep every CU busy just as the previous picture's
@@ -404,9 +353,9 @@ void GpuH264Encoder::ensure_me_stream() {
     if (reserve > 0 && reserve < ncu) {
         std::vector<uint32_t> mask((size_t)(ncu + 31) / 32, 0u);
         for (int c = 0; c < ncu - reserve; ++c) mask[(size_t)c / 32] |= 1u << (c % 32);
-        HIP_CHECK(hipExtStreamCreateWithCUMask(&stream_m_, (uint32_t)mask.size(), mask.data()));
+        stream_m_ = res_.stream_cu_mask(mask);
     } else {
-        HIP_CHECK(hipStreamCreateWithFlags(&stream_m_, hipStreamNonBlocking));
+        stream_m_ = res_.stream(hipStreamNonBlocking);
     }
 }
 
@@ -465,26 +414,8 @@ GpuH264Encoder::~GpuH264Encoder() {
         launcher_.join();
     }
     (void)hipStreamSynchronize(stream_);
-    if (stream_e_) {
-        (void)hipStreamSynchronize(stream_e_);
-        (void)hipStreamDestroy(stream_e_);
-    }
-    if (stream_e2_) {
-        (void)hipStreamSynchronize(stream_e2_);
-        (void)hipStreamDestroy(stream_e2_);
-    }
-    if (stream_m_) {
-        (void)hipStreamSynchronize(stream_m_);
-        (void)hipStreamDestroy(stream_m_);
-    }
-    if (ev_hpu_) (void)hipEventDestroy(ev_hpu_);
-    if (rec_unf_) (void)hipFree(rec_unf_);
-    for (int i = 0; i < 2; ++i) {
-        (void)hipFree(rec_y_[i]);
-        (void)hipFree(rec_uv_[i]);
-        (void)hipFree(src_keep_[i]);
-    }
-    for (int i = 0; i < depth_; ++i) free_slot(slots_[i]);
+    for (hipStream_t s : {stream_e_, stream_e2_, stream_m_})
+        if (s) (void)hipStreamSynchronize(s);
 }
 
 bool GpuH264Encoder::enqueue_analysis_kernels(bool idr, const uint8_t* src_y, const uint8_t* src_uv, bool publish,
@@ -579,7 +510,7 @@ void GpuH264Encoder::enqueue_kernels(bool idr, const uint8_t* src_y, const uint8
         }
         // depth >= 3: the chains of consecutive pictures alternate between two entropy streams
         if (depth_ >= 3 && !stream_e2_ && !e2_retired_ && !stream_m_)
-            HIP_CHECK(hipStreamCreateWithFlags(&stream_e2_, hipStreamNonBlocking));
+            stream_e2_ = res_.stream(hipStreamNonBlocking);
         hipStream_t es = (stream_e2_ && (seq_ & 1)) ? stream_e2_ : stream_e_;
         HIP_CHECK(hipGetLastError());
         {

@@ -19,6 +19,7 @@
 #include <thread>
 #include <vector>
 
+#include "../common/gpu_arena.h"
 #include "h264_core.h"
 #include "h264_deblock.h"
 #include "h264_gpu.h"
@@ -329,6 +330,7 @@ class GpuH264Encoder final : public VideoEncoder {
 
    private:
     struct FrameSlot {  // per-frame-in-flight state
+        GpuArena res;  // owns the slot's buffers and events: first, so it outlives what uses them
         DeviceBuffers buf{};
         FrameState* fs_host = nullptr;  // pinned
         uint8_t* host_out = nullptr;    // pinned, mapped: OutHeader | slice tables | payload
@@ -342,7 +344,6 @@ class GpuH264Encoder final : public VideoEncoder {
         ScrollBuffers scroll;          // scroll hint of this slot's picture (EncoderConfig::scroll_range)
     };
     void alloc_slot(FrameSlot& sl);
-    void free_slot(FrameSlot& sl);
     void fill_state(FrameSlot& sl, bool idr, int qp, int ref, int cur);
     void unfiltered_copy(FrameSlot& sl);
     void ensure_me_stream();
@@ -360,6 +361,9 @@ class GpuH264Encoder final : public VideoEncoder {
     void launcher_loop();
     void wait_launched(int slot) const;  // the job whose k_pack carries slots_[slot].done was issued
     void drain_launcher() const;         // every queued job issued
+    // Owns the picture-wide buffers, ev_hpu_ and the streams this encoder creates.  Declared before
+    // launcher_ and slots_, which use its handles, so it is destroyed after them.
+    GpuArena res_;
     std::thread launcher_;
     mutable std::mutex lmu_;
     mutable std::condition_variable lcv_;

@@ -160,6 +160,35 @@ struct Geometry {
     int pitch;          // luma pitch (bytes); UV plane has the same pitch
     int coded_w, coded_h;  // mb_w*16, mb_h*16
 };
+// The geometry of a width x height picture of unit_w x unit_h 16x16 units (macroblocks, HEVC units).
+inline Geometry make_geometry(int width, int height, int unit_w, int unit_h) {
+    Geometry g{};
+    g.width = width;
+    g.height = height;
+    g.mb_w = unit_w;
+    g.mb_h = unit_h;
+    g.coded_w = unit_w * 16;
+    g.coded_h = unit_h * 16;
+    g.pitch = (g.coded_w + 255) & ~255;
+    return g;
+}
+// The quality-report mask (x0, y0, x1, y1 in samples; x1 <= x0 or y1 <= y0: none) widened to whole
+// units into r (left as it is without a mask); returns the picture's samples outside those units.
+inline int64_t mask_units(const Geometry& g, int x0, int y0, int x1, int y1, int r[4]) {
+    const auto lo = [](int a, int b) { return a < b ? a : b; };
+    const auto hi = [](int a, int b) { return a > b ? a : b; };
+    if (x1 > x0 && y1 > y0) {
+        r[0] = hi(0, x0) / 16;
+        r[1] = hi(0, y0) / 16;
+        r[2] = lo(g.mb_w, (x1 + 15) / 16);
+        r[3] = lo(g.mb_h, (y1 + 15) / 16);
+    }
+    int64_t outside = (int64_t)g.width * g.height;
+    for (int uy = r[1]; uy < r[3]; ++uy)
+        for (int ux = r[0]; ux < r[2]; ++ux)
+            outside -= (int64_t)hi(0, lo(16, g.width - 16 * ux)) * hi(0, lo(16, g.height - 16 * uy));
+    return outside;
+}
 
 // Device buffers owned by the GPU encoder.
 struct DeviceBuffers {

@@ -20,82 +20,62 @@ void GpuHevcEncoder::alloc_slot(FrameSlot& sl) {
     // substreams: cost-balanced slices, or (WPP) every CTB row
     const int ns = cfg_.hevc_wpp ? std::max(common_.max_slices(), common_.c32_h()) : common_.max_slices();
     HevcDeviceBuffers& b = sl.buf;
-    HIP_CHECK(hipMalloc(&b.fs, sizeof(HevcFrameState)));
-    HIP_CHECK(hipMalloc(&b.me.fs, sizeof(h264::FrameState)));
-    HIP_CHECK(hipMalloc(&b.me.mb, sizeof(h264::MbInfo) * ncu));
-    HIP_CHECK(hipMemsetAsync(b.me.mb, 0, sizeof(h264::MbInfo) * ncu, stream_));
-    HIP_CHECK(hipMalloc(&b.cu, sizeof(CuInfo) * ncu));
-    HIP_CHECK(hipMalloc(&b.coef, sizeof(int16_t) * kCoefPerCu * (size_t)ncu));
+    GpuArena& r = sl.res;
+    b.fs = r.device<HevcFrameState>(1);
+    b.me.fs = r.device<h264::FrameState>(1);
+    b.me.mb = r.device_fill<h264::MbInfo>(ncu, 0, stream_);
+    b.cu = r.device<CuInfo>(ncu);
+    b.coef = r.device<int16_t>(kCoefPerCu * (size_t)ncu);
     // per-substream CABAC output slot: room for 1 KiB per unit of an even share of the picture plus
     // one slice of CTB rows (slices are cost-balanced, so a slice of many cheap CTBs stays small)
     const size_t units_per_slot = std::max((size_t)(ncu + ns - 1) / ns + (size_t)2 * common_.slice_rows() * geom_.mb_w,
                                            (size_t)2 * geom_.mb_w);
     b.slice_cap = (uint32_t)((units_per_slot * 1024 + 15) & ~(size_t)15);
-    HIP_CHECK(hipMalloc(&b.slice_data, (size_t)b.slice_cap * ns));
-    HIP_CHECK(hipMalloc(&b.slice_len, sizeof(uint32_t) * ns));
-    HIP_CHECK(hipMalloc(&b.slice_first, sizeof(int) * ns));
-    HIP_CHECK(hipMalloc(&b.slice_of_cu, sizeof(int) * nctb));
-    HIP_CHECK(hipMalloc(&b.nslices, sizeof(uint32_t)));
-    HIP_CHECK(hipMalloc(&b.qpy, ncu));
-    HIP_CHECK(hipMalloc(&b.qp_pred, ncu));
-    HIP_CHECK(hipMalloc(&b.imode, ncu));
-    HIP_CHECK(hipMalloc(&b.itu4, ncu));
+    b.slice_data = r.device<uint8_t>((size_t)b.slice_cap * ns);
+    b.slice_len = r.device<uint32_t>(ns);
+    b.slice_first = r.device<int>(ns);
+    b.slice_of_cu = r.device<int>(nctb);
+    b.nslices = r.device<uint32_t>(1);
+    b.qpy = r.device<uint8_t>(ncu);
+    b.qp_pred = r.device<uint8_t>(ncu);
+    b.imode = r.device<uint8_t>(ncu);
+    b.itu4 = r.device<uint8_t>(ncu);
     if (cfg_.hevc_intra_in_p) {
-        HIP_CHECK(hipMalloc(&b.isatd, sizeof(uint32_t) * ncu));
-        HIP_CHECK(hipMalloc(&b.igain, sizeof(int32_t) * ncu));
-        HIP_CHECK(hipMalloc(&b.ipmode, ncu));
-        HIP_CHECK(hipMalloc(&b.isel, ncu));
+        b.isatd = r.device<uint32_t>(ncu);
+        b.igain = r.device<int32_t>(ncu);
+        b.ipmode = r.device<uint8_t>(ncu);
+        b.isel = r.device<uint8_t>(ncu);
     }
     // arrays scanned in 4096-entry tiles of 16-byte loads (per CTB costs, per coding position token
     // counts): padded with zeros to a whole tile
     auto pad = [](size_t n) { return (n + kScanTilePad - 1) / kScanTilePad * kScanTilePad + 4; };
     const size_t nctb_pad = pad((size_t)nctb), npos_pad = pad((size_t)npos);
-    HIP_CHECK(hipMalloc(&b.cost, sizeof(uint32_t) * nctb_pad));
-    HIP_CHECK(hipMemsetAsync(b.cost, 0, sizeof(uint32_t) * nctb_pad, stream_));
-    HIP_CHECK(hipMalloc(&b.qpc, ncu));
-    HIP_CHECK(hipMalloc(&b.sao, sizeof(uint32_t) * 4 * (size_t)nctb));
-    HIP_CHECK(hipMalloc(&b.slice_clk, sizeof(unsigned long long) * 2 * (size_t)ns));
-    HIP_CHECK(hipMalloc(&b.tok, sizeof(uint16_t) * kMaxCuTokens * (size_t)npos));
-    HIP_CHECK(hipMalloc(&b.ntok, sizeof(uint32_t) * npos_pad));
-    HIP_CHECK(hipMemsetAsync(b.ntok, 0, sizeof(uint32_t) * npos_pad, stream_));
-    HIP_CHECK(hipMalloc(&b.tok_off, sizeof(uint32_t) * npos_pad));
+    b.cost = r.device_fill<uint32_t>(nctb_pad, 0, stream_);
+    b.qpc = r.device<uint8_t>(ncu);
+    b.sao = r.device<uint32_t>(4 * (size_t)nctb);
+    b.slice_clk = r.device<unsigned long long>(2 * (size_t)ns);
+    b.tok = r.device<uint16_t>(kMaxCuTokens * (size_t)npos);
+    b.ntok = r.device_fill<uint32_t>(npos_pad, 0, stream_);
+    b.tok_off = r.device<uint32_t>(npos_pad);
     // + one chunk of padding: k_hevc_arith reads whole 256-token chunks
-    HIP_CHECK(hipMalloc(&b.tok_dense, sizeof(uint16_t) * (kMaxCuTokens * (size_t)npos + 512)));
-    HIP_CHECK(hipMalloc(&b.sse_part, 4 * sizeof(unsigned long long) * h264::kSsePartStride));
-    HIP_CHECK(hipMalloc(&b.sse_tot, kSseSlots * kSseSlotWords * sizeof(unsigned long long)));
-    HIP_CHECK(hipMalloc(&b.pack_done, sizeof(uint32_t)));
-    HIP_CHECK(hipMemsetAsync(b.pack_done, 0, sizeof(uint32_t), stream_));
-    HIP_CHECK(hipMalloc(&b.wpp_ctx, sizeof(uint32_t) * kWppCtxWords * (size_t)common_.c32_h()));
-    HIP_CHECK(hipMalloc(&b.wpp_flag, sizeof(uint32_t) * (size_t)common_.c32_h()));
-    HIP_CHECK(hipMemsetAsync(b.wpp_flag, 0, sizeof(uint32_t) * (size_t)common_.c32_h(), stream_));
+    b.tok_dense = r.device<uint16_t>(kMaxCuTokens * (size_t)npos + 512);
+    b.sse_part = r.device<unsigned long long>(4 * (size_t)h264::kSsePartStride);
+    b.sse_tot = r.device<unsigned long long>(kSseSlots * kSseSlotWords);
+    b.pack_done = r.device_fill<uint32_t>(1, 0, stream_);
+    b.wpp_ctx = r.device<uint32_t>(kWppCtxWords * (size_t)common_.c32_h());
+    b.wpp_flag = r.device_fill<uint32_t>(common_.c32_h(), 0, stream_);
     b.db_state = db_state_;
-    HIP_CHECK(hipHostMalloc(&b.wpp_err, sizeof(int), hipHostMallocMapped));
+    b.wpp_err = r.pinned<int>(1, hipHostMallocMapped);
     *b.wpp_err = 0;
     b.out_bytes = (size_t)ncu * 768;
-    HIP_CHECK(hipHostMalloc(&sl.fs_host, sizeof(HevcFrameState), hipHostMallocDefault));
-    HIP_CHECK(hipHostMalloc(&sl.me_fs_host, sizeof(h264::FrameState), hipHostMallocDefault));
+    sl.fs_host = r.pinned<HevcFrameState>(1, hipHostMallocDefault);
+    sl.me_fs_host = r.pinned<h264::FrameState>(1, hipHostMallocDefault);
     std::memset(sl.me_fs_host, 0, sizeof(h264::FrameState));
-    HIP_CHECK(hipHostMalloc(&sl.host_out, kOutPayloadOffset + b.out_bytes + 16, hipHostMallocMapped));
+    sl.host_out = r.pinned<uint8_t>(kOutPayloadOffset + b.out_bytes + 16, hipHostMallocMapped);
     std::memset(sl.host_out, 0, kOutPayloadOffset);
-    HIP_CHECK(hipEventCreate(&sl.start));
-    HIP_CHECK(hipEventCreateWithFlags(&sl.analysis_done, hipEventDisableTiming));
-    HIP_CHECK(hipEventCreate(&sl.done));
-}
-
-void GpuHevcEncoder::free_slot(FrameSlot& sl) {
-    HevcDeviceBuffers& b = sl.buf;
-    for (void* p : {(void*)b.fs, (void*)b.me.fs, (void*)b.me.mb, (void*)b.cu, (void*)b.coef, (void*)b.slice_data,
-                    (void*)b.slice_len, (void*)b.slice_first, (void*)b.slice_of_cu, (void*)b.nslices, (void*)b.qpy, (void*)b.qp_pred, (void*)b.imode, (void*)b.itu4, (void*)b.cost, (void*)b.qpc,
-                    (void*)b.sse_part, (void*)b.sse_tot, (void*)b.sao, (void*)b.slice_clk, (void*)b.tok, (void*)b.ntok, (void*)b.tok_off,
-                    (void*)b.tok_dense, (void*)b.wpp_ctx, (void*)b.wpp_flag, (void*)b.pack_done, (void*)b.isatd,
-                    (void*)b.igain, (void*)b.ipmode, (void*)b.isel})
-        if (p) (void)hipFree(p);
-    if (b.wpp_err) (void)hipHostFree(b.wpp_err);
-    if (sl.fs_host) (void)hipHostFree(sl.fs_host);
-    if (sl.me_fs_host) (void)hipHostFree(sl.me_fs_host);
-    if (sl.host_out) (void)hipHostFree(sl.host_out);
-    for (hipEvent_t e : {sl.start, sl.analysis_done, sl.done})
-        if (e) (void)hipEventDestroy(e);
+    sl.start = r.event(0);
+    sl.analysis_done = r.event(hipEventDisableTiming);
+    sl.done = r.event(0);
 }
 
 GpuHevcEncoder::GpuHevcEncoder(const EncoderConfig& cfg, hipStream_t stream)
@@ -104,13 +84,8 @@ GpuHevcEncoder::GpuHevcEncoder(const EncoderConfig& cfg, hipStream_t stream)
         throw std::invalid_argument("pipeline_depth must be 1, 2 or 3");
     if (2 * common_.slice_rows() > kMaxSliceRows) throw std::invalid_argument("hevc: too many CTB rows per slice");
     depth_ = cfg.pipeline_depth;
-    geom_.width = cfg.width;
-    geom_.height = cfg.height;
-    geom_.mb_w = common_.ctb_w();
-    geom_.mb_h = common_.ctb_h();
-    geom_.coded_w = geom_.mb_w * kCtb;
-    geom_.coded_h = geom_.mb_h * kCtb;
-    geom_.pitch = (geom_.coded_w + 255) & ~255;
+    static_assert(kCtb == 16, "the analysis unit is the 16x16 unit of h264::Geometry");
+    geom_ = h264::make_geometry(cfg.width, cfg.height, common_.ctb_w(), common_.ctb_h());
     const int ncu = geom_.mb_w * geom_.mb_h;
     if (std::max((ncu + 3) / 4, common_.num_ctbs()) > h264::kSsePartStride)
         throw std::invalid_argument("frame too large for the distortion partials");
@@ -118,33 +93,20 @@ GpuHevcEncoder::GpuHevcEncoder(const EncoderConfig& cfg, hipStream_t stream)
     bl_safe_split_ = bl_safe_split();
     const size_t ysz = (size_t)geom_.pitch * geom_.coded_h, uvsz = ysz / 2;
     for (int i = 0; i < 2; ++i) {
-        HIP_CHECK(hipMalloc(&rec_y_[i], ysz));
-        HIP_CHECK(hipMalloc(&rec_uv_[i], uvsz));
-        HIP_CHECK(hipMemsetAsync(rec_y_[i], 16, ysz, stream_));
-        HIP_CHECK(hipMemsetAsync(rec_uv_[i], 128, uvsz, stream_));
-        HIP_CHECK(hipMalloc(&src_keep_[i], ysz));
-        HIP_CHECK(hipMemsetAsync(src_keep_[i], 16, ysz, stream_));
+        rec_y_[i] = res_.device_fill<uint8_t>(ysz, 16, stream_);
+        rec_uv_[i] = res_.device_fill<uint8_t>(uvsz, 128, stream_);
+        src_keep_[i] = res_.device_fill<uint8_t>(ysz, 16, stream_);
     }
     if (cfg.sao) {
-        HIP_CHECK(hipMalloc(&pre_y_, ysz));
-        HIP_CHECK(hipMalloc(&pre_uv_, uvsz));
+        pre_y_ = res_.device<uint8_t>(ysz);
+        pre_uv_ = res_.device<uint8_t>(uvsz);
     }
-    if (cfg.mask_x1 > cfg.mask_x0 && cfg.mask_y1 > cfg.mask_y0) {  // CTB = 16: the H.264 MB-aligned region
-        mask_c_[0] = std::max(0, cfg.mask_x0) / kCtb;
-        mask_c_[1] = std::max(0, cfg.mask_y0) / kCtb;
-        mask_c_[2] = std::min(geom_.mb_w, (cfg.mask_x1 + kCtb - 1) / kCtb);
-        mask_c_[3] = std::min(geom_.mb_h, (cfg.mask_y1 + kCtb - 1) / kCtb);
-    }
-    masked_pixels_ = (int64_t)cfg.width * cfg.height;
-    for (int cy = mask_c_[1]; cy < mask_c_[3]; ++cy)
-        for (int cx = mask_c_[0]; cx < mask_c_[2]; ++cx)
-            masked_pixels_ -= (int64_t)std::max(0, std::min(kCtb, cfg.width - kCtb * cx)) *
-                              std::max(0, std::min(kCtb, cfg.height - kCtb * cy));
+    // CTB = 16: the H.264 MB-aligned region
+    masked_pixels_ = h264::mask_units(geom_, cfg.mask_x0, cfg.mask_y0, cfg.mask_x1, cfg.mask_y1, mask_c_);
     hp_pitch_ = (geom_.coded_w + 2 * h264::kHpelPad + 255) & ~255;
     const size_t hp_bytes = (size_t)hp_pitch_ * (geom_.coded_h + 2 * h264::kHpelPad);
-    for (int i = 0; i < 4; ++i) HIP_CHECK(hipMalloc(&hp_[i], hp_bytes));
-    HIP_CHECK(hipMalloc(&db_state_, sizeof(uint32_t) * 4));
-    HIP_CHECK(hipMemsetAsync(db_state_, 0, sizeof(uint32_t) * 4, stream_));
+    for (int i = 0; i < 4; ++i) hp_[i] = res_.device<uint8_t>(hp_bytes);
+    db_state_ = res_.device_fill<uint32_t>(4, 0, stream_);
     for (int i = 0; i < depth_; ++i) alloc_slot(slots_[i]);
     if (depth_ > 1) {
         // entropy streams: MXDESK_HEVC_ESTREAMS of them, slots beyond share them round-robin.  Every
@@ -157,7 +119,7 @@ GpuHevcEncoder::GpuHevcEncoder(const EncoderConfig& cfg, hipStream_t stream)
         const char* hq = std::getenv("GPU_MAX_HW_QUEUES");
         const int queues = hq && std::atoi(hq) > 0 ? std::atoi(hq) : 4;
         n_es_ = std::clamp(ne ? std::atoi(ne) : std::min(depth_, queues - 2), 1, depth_);
-        for (int i = 0; i < n_es_; ++i) HIP_CHECK(hipStreamCreateWithFlags(&stream_e_[i], hipStreamNonBlocking));
+        for (int i = 0; i < n_es_; ++i) stream_e_[i] = res_.stream(hipStreamNonBlocking);
         for (int i = n_es_; i < depth_; ++i) stream_e_[i] = stream_e_[i % n_es_];
     }
     clock_khz_ = device_clock_khz();
@@ -166,20 +128,7 @@ GpuHevcEncoder::GpuHevcEncoder(const EncoderConfig& cfg, hipStream_t stream)
 
 GpuHevcEncoder::~GpuHevcEncoder() {
     (void)hipStreamSynchronize(stream_);
-    for (int i = 0; i < n_es_; ++i) {
-        (void)hipStreamSynchronize(stream_e_[i]);
-        (void)hipStreamDestroy(stream_e_[i]);
-    }
-    for (int i = 0; i < 2; ++i) {
-        (void)hipFree(rec_y_[i]);
-        (void)hipFree(rec_uv_[i]);
-        (void)hipFree(src_keep_[i]);
-    }
-    for (int i = 0; i < 4; ++i) (void)hipFree(hp_[i]);
-    if (pre_y_) (void)hipFree(pre_y_);
-    if (pre_uv_) (void)hipFree(pre_uv_);
-    for (int i = 0; i < depth_; ++i) free_slot(slots_[i]);
-    if (db_state_) (void)hipFree(db_state_);
+    for (int i = 0; i < n_es_; ++i) (void)hipStreamSynchronize(stream_e_[i]);
 }
 
 void GpuHevcEncoder::fill_state(FrameSlot& sl, bool idr, int qp, int ref, int cur, bool probe) {

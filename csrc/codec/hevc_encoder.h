@@ -348,6 +348,7 @@ class GpuHevcEncoder final : public VideoEncoder {
 
    private:
     struct FrameSlot {
+        GpuArena res;  // owns the slot's buffers and events: first, so it outlives what uses them
         HevcDeviceBuffers buf{};
         HevcFrameState* fs_host = nullptr;     // pinned
         h264::FrameState* me_fs_host = nullptr;  // pinned
@@ -358,10 +359,13 @@ class GpuHevcEncoder final : public VideoEncoder {
         int poc = 0;
     };
     void alloc_slot(FrameSlot& sl);
-    void free_slot(FrameSlot& sl);
     void fill_state(FrameSlot& sl, bool idr, int qp, int ref, int cur, bool probe = false);
     int probe_bytes(const uint8_t* src_y, const uint8_t* src_uv, int qp);
 
+    // Owns the picture-wide buffers and the entropy streams (the first n_es_ entries of stream_e_; the
+    // entries beyond alias them).  Declared before slots_, which uses its handles, so it is destroyed
+    // after it.
+    GpuArena res_;
     EncoderConfig cfg_;
     HevcCommon common_;
     hipStream_t stream_;

@@ -375,6 +375,9 @@ class GpuVp8Encoder final : public VideoEncoder {
     // token partitions by then: the writer codes the first partition itself and puts the frame
     // together, and the pool exists only once a partition overflowed its region (recode_on_host).
     struct Slot {
+        // owns the slot's buffers and events (lv_host and redo appear on the slot's writer thread);
+        // first, so it outlives what uses them
+        GpuArena res;
         Vp8DeviceBuffers buf{};
         Vp8States* st_host = nullptr;  // pinned: copied to buf.st at the start of the frame
         hipEvent_t start = nullptr, done = nullptr;
@@ -398,13 +401,15 @@ class GpuVp8Encoder final : public VideoEncoder {
         double wt_us = 0;  // writer time (MXDESK_HOST_TIMING report)
         long long wt_n = 0;
     };
+    // Owns the picture-wide planes.  Declared before slots_ and its writer threads, which use its
+    // handles, so it is destroyed after them.
+    GpuArena res_;
     std::unique_ptr<PartitionPool> pool_;
     std::once_flag pool_once_;
     bool gpu_tokens_ = false;
     std::atomic<long long> tok_fallbacks_{0};
     void writer_loop(Slot& s);
     void alloc_slot(Slot& s);
-    void free_slot(Slot& s);
     void fill_state(Slot& s, bool key, int qp, int ref, int cur);
     int probe_bytes(const uint8_t* src_y, const uint8_t* src_uv, int qp);
     void check_slot(Slot& s);

@@ -54,49 +54,38 @@ constexpr size_t kTokBytesAt = sizeof(Vp8TokenHeader) + sizeof(uint32_t) * 2 * k
 void GpuVp8Encoder::alloc_slot(Slot& s) {
     const int nmb = geom_.mb_w * geom_.mb_h;
     Vp8DeviceBuffers& b = s.buf;
-    HIP_CHECK(hipMalloc(&b.st, sizeof(Vp8States)));
-    HIP_CHECK(hipMalloc(&b.mb, sizeof(Vp8Mb) * (size_t)nmb));
-    HIP_CHECK(hipMalloc(&b.lv, sizeof(int16_t) * kCoefPerMb * (size_t)nmb));
-    HIP_CHECK(hipMalloc(&b.line, sizeof(uint64_t) * kKeyLineWords * (size_t)geom_.mb_h * geom_.mb_w));
-    HIP_CHECK(hipMemsetAsync(b.line, 0, sizeof(uint64_t) * kKeyLineWords * (size_t)geom_.mb_h * geom_.mb_w, stream_));  // tag 0: no frame
+    GpuArena& r = s.res;
+    b.st = r.device<Vp8States>(1);
+    b.mb = r.device<Vp8Mb>(nmb);
+    b.lv = r.device<int16_t>(kCoefPerMb * (size_t)nmb);
+    b.line = r.device_fill<uint64_t>(kKeyLineWords * (size_t)geom_.mb_h * geom_.mb_w, 0, stream_);  // tag 0: no frame
     // hand-off lines: 32 tagged words per macroblock per workgroup of rows, then 1 KB scratch per
     // row (k_vp8_lf); tags start at 0, never a frame's epoch
-    const size_t lf_bytes = sizeof(uint64_t) * 32 * (size_t)geom_.mb_h * geom_.mb_w + 1024 * (size_t)(geom_.mb_h + 16);
-    HIP_CHECK(hipMalloc(&b.lf_line, lf_bytes));
-    HIP_CHECK(hipMemsetAsync(b.lf_line, 0, lf_bytes, stream_));
-    HIP_CHECK(hipHostMalloc(&b.lf_sse, sizeof(unsigned long long) * 3 * (size_t)geom_.mb_h, hipHostMallocMapped));
-    HIP_CHECK(hipHostMalloc(&b.err, sizeof(int), hipHostMallocMapped));
+    const size_t lf_words = 32 * (size_t)geom_.mb_h * geom_.mb_w + 1024 / sizeof(uint64_t) * (size_t)(geom_.mb_h + 16);
+    b.lf_line = r.device_fill<unsigned long long>(lf_words, 0, stream_);
+    b.lf_sse = r.pinned<unsigned long long>(3 * (size_t)geom_.mb_h, hipHostMallocMapped);
+    b.err = r.pinned<int>(1, hipHostMallocMapped);
     *b.err = 0;
-    HIP_CHECK(hipHostMalloc(&b.mb_host, sizeof(Vp8Mb) * (size_t)nmb, hipHostMallocMapped));
+    b.mb_host = r.pinned<Vp8Mb>(nmb, hipHostMallocMapped);
     if (gpu_tokens_) {  // the levels stay on the GPU (recode_on_host allocates lv_host if it ever runs)
         const int nparts = 1 << log2_parts_, rows = (geom_.mb_h + nparts - 1) / nparts;
         const size_t region = ((size_t)cfg_.vp8_tokens_cap * geom_.mb_w * rows + 3) & ~(size_t)3;
         if (region > 0x7fffffffu) throw std::invalid_argument("vp8_tokens_cap too large");
         b.tok_region = (uint32_t)region;
-        HIP_CHECK(hipHostMalloc(&b.tok_out, kTokBytesAt + region * nparts, hipHostMallocMapped));
+        b.tok_out = r.pinned<uint8_t>(kTokBytesAt + region * nparts, hipHostMallocMapped);
         std::memset(b.tok_out, 0, kTokBytesAt);
         s.upd.assign(kNumCoefProbs, 0);
     } else {
-        HIP_CHECK(hipHostMalloc(&b.lv_host, sizeof(int16_t) * kCoefPerMb * (size_t)nmb, hipHostMallocMapped));
+        b.lv_host = r.pinned<int16_t>(kCoefPerMb * (size_t)nmb, hipHostMallocMapped);
     }
-    HIP_CHECK(hipMalloc(&b.me.mb, sizeof(h264::MbInfo) * (size_t)nmb));
-    HIP_CHECK(hipMalloc(&b.icand, (size_t)nmb));
-    HIP_CHECK(hipMalloc(&b.ilist, sizeof(int) * (size_t)(nmb + 1)));
+    b.me.mb = r.device<h264::MbInfo>(nmb);
+    b.icand = r.device<uint8_t>(nmb);
+    b.ilist = r.device<int>((size_t)nmb + 1);
     b.me.fs = &b.st->me;
-    HIP_CHECK(hipHostMalloc(&s.st_host, sizeof(Vp8States), hipHostMallocDefault));
+    s.st_host = r.pinned<Vp8States>(1, hipHostMallocDefault);
     std::memset(s.st_host, 0, sizeof(Vp8States));
-    HIP_CHECK(hipEventCreate(&s.start));
-    HIP_CHECK(hipEventCreate(&s.done));
-}
-
-void GpuVp8Encoder::free_slot(Slot& s) {
-    Vp8DeviceBuffers& b = s.buf;
-    for (void* p : {(void*)b.st, (void*)b.mb, (void*)b.lv, (void*)b.line, (void*)b.me.mb, (void*)b.lf_line, (void*)b.icand, (void*)b.ilist})
-        if (p) (void)hipFree(p);
-    for (void* p : {(void*)b.err, (void*)b.mb_host, (void*)b.lv_host, (void*)s.st_host, (void*)b.lf_sse, (void*)b.tok_out})
-        if (p) (void)hipHostFree(p);
-    for (hipEvent_t e : {s.start, s.done, s.redo})
-        if (e) (void)hipEventDestroy(e);
+    s.start = r.event(0);
+    s.done = r.event(0);
 }
 
 GpuVp8Encoder::GpuVp8Encoder(const h264::EncoderConfig& cfg, hipStream_t stream)
@@ -109,32 +98,22 @@ GpuVp8Encoder::GpuVp8Encoder(const h264::EncoderConfig& cfg, hipStream_t stream)
         throw std::invalid_argument("pipeline_depth must be 1 to 4");
     if (cfg.width > 16383 || cfg.height > 16383) throw std::invalid_argument("vp8: picture larger than 16383");
     depth_ = cfg.pipeline_depth;
-    geom_.width = cfg.width;
-    geom_.height = cfg.height;
-    geom_.mb_w = common_.mb_w();
-    geom_.mb_h = common_.mb_h();
-    geom_.coded_w = geom_.mb_w * 16;
-    geom_.coded_h = geom_.mb_h * 16;
-    geom_.pitch = (geom_.coded_w + 255) & ~255;
+    geom_ = h264::make_geometry(cfg.width, cfg.height, common_.mb_w(), common_.mb_h());
     if (geom_.mb_w > 512) throw std::invalid_argument("vp8: picture too wide (k_vp8_gather ranks <= 512 MBs per row)");
     log2_parts_ = log2_parts_for(geom_.mb_h);
     gpu_tokens_ = gpu_tokens_from(cfg.vp8_tokens);
     if (gpu_tokens_ && cfg.vp8_tokens_cap < 1) throw std::invalid_argument("vp8_tokens_cap must be at least 1");
     const size_t ysz = (size_t)geom_.pitch * geom_.coded_h, uvsz = ysz / 2;
     for (int i = 0; i < 2; ++i) {
-        HIP_CHECK(hipMalloc(&rec_y_[i], ysz));
-        HIP_CHECK(hipMalloc(&rec_uv_[i], uvsz));
-        HIP_CHECK(hipMemsetAsync(rec_y_[i], 0, ysz, stream_));
-        HIP_CHECK(hipMemsetAsync(rec_uv_[i], 128, uvsz, stream_));
-        if (cfg_.aq >= 3) {
-            HIP_CHECK(hipMalloc(&src_keep_[i], ysz));
-            HIP_CHECK(hipMemsetAsync(src_keep_[i], 0, ysz, stream_));
-        }
+        rec_y_[i] = res_.device_fill<uint8_t>(ysz, 0, stream_);
+        rec_uv_[i] = res_.device_fill<uint8_t>(uvsz, 128, stream_);
+        if (cfg_.aq >= 3) src_keep_[i] = res_.device_fill<uint8_t>(ysz, 0, stream_);
     }
     hp_pitch_ = (geom_.coded_w + 2 * h264::kHpelPad + 255) & ~255;
-    HIP_CHECK(hipMalloc(&hp_, (size_t)hp_pitch_ * (geom_.coded_h + 2 * h264::kHpelPad)));
+    const size_t hp_bytes = (size_t)hp_pitch_ * (geom_.coded_h + 2 * h264::kHpelPad);
+    hp_ = res_.device<uint8_t>(hp_bytes);
     if (cfg.subpel)
-        for (auto& p : hp_sub_) HIP_CHECK(hipMalloc(&p, (size_t)hp_pitch_ * (geom_.coded_h + 2 * h264::kHpelPad)));
+        for (auto& p : hp_sub_) p = res_.device<uint8_t>(hp_bytes);
     for (int i = 0; i < depth_; ++i) alloc_slot(slots_[i]);
     HIP_CHECK(hipStreamSynchronize(stream_));
     HIP_CHECK(hipGetDevice(&device_));
@@ -216,15 +195,6 @@ GpuVp8Encoder::~GpuVp8Encoder() {
     if (wt_n > 0 && std::getenv("MXDESK_HOST_TIMING"))
         std::fprintf(stderr, "[mxdesk] vp8 bitstream writer: %.1f us/frame over %lld frames\n", wt_us / wt_n, wt_n);
     (void)hipStreamSynchronize(stream_);
-    for (int i = 0; i < 2; ++i) {
-        (void)hipFree(rec_y_[i]);
-        (void)hipFree(rec_uv_[i]);
-        if (src_keep_[i]) (void)hipFree(src_keep_[i]);
-    }
-    (void)hipFree(hp_);
-    for (auto p : hp_sub_)
-        if (p) (void)hipFree(p);
-    for (int i = 0; i < depth_; ++i) free_slot(slots_[i]);
 }
 
 void GpuVp8Encoder::fill_state(Slot& s, bool key, int qp, int ref, int cur) {
@@ -340,9 +310,8 @@ void GpuVp8Encoder::recode_on_host(Slot& s, std::vector<uint8_t>& out, bool prob
     // level-carrying gather and the host writer code the frame as with vp8_tokens 0
     Vp8DeviceBuffers& b = s.buf;
     ++tok_fallbacks_;
-    if (!b.lv_host)
-        HIP_CHECK(hipHostMalloc(&b.lv_host, sizeof(int16_t) * kCoefPerMb * (size_t)geom_.mb_w * geom_.mb_h, hipHostMallocMapped));
-    if (!s.redo) HIP_CHECK(hipEventCreate(&s.redo));
+    if (!b.lv_host) b.lv_host = s.res.pinned<int16_t>(kCoefPerMb * (size_t)geom_.mb_w * geom_.mb_h, hipHostMallocMapped);
+    if (!s.redo) s.redo = s.res.event(0);
     launch_vp8_gather(geom_, b, stream_, true);
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipEventRecord(s.redo, stream_));

@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 namespace mx {
+class GpuArena;  // common/gpu_arena.h
 namespace pix {
 
 // Parameters of the synthetic desktop frame (animated noise + gears + scrolling text +
@@ -94,8 +95,8 @@ struct ScaleFragsHost {
 bool build_scale_frags(int in_w, int in_h, int out_w, int out_h, int coded_w, int coded_h,
                        const std::vector<int>& x0, const std::vector<float>& wx, int tx, const std::vector<int>& y0,
                        const std::vector<float>& wy, int ty, ScaleFragsHost& out);
-// Copies the blob to `dev` (hipMalloc'ed here; caller frees) and fills `mf`.
-void upload_scale_frags(const ScaleFragsHost& h, void** dev, ScaleMfma& mf);
+// Copies the blob to device memory of `res` and fills `mf` with pointers into it.
+void upload_scale_frags(const ScaleFragsHost& h, GpuArena& res, ScaleMfma& mf);
 // LDS bytes of one VALU-kernel tile (k_scale_to_nv12) for this geometry, and the footprint it is
 // sized for: max_nc staged columns (whole quads) x max_nr rows.
 size_t scale_valu_lds_bytes(int in_w, int in_h, int out_w, int out_h, int taps_x, int taps_y, int* max_nc = nullptr,

@@ -19,6 +19,7 @@
 #include <type_traits>
 
 #include "pixel.h"
+#include "../common/gpu_arena.h"
 #include "../common/hip_check.h"
 #include "../common/launch_event.h"
 
@@ -1448,11 +1449,10 @@ bool build_scale_frags(int in_w, int in_h, int out_w, int out_h, int coded_w, in
     return true;
 }
 
-void upload_scale_frags(const ScaleFragsHost& h, void** dev, ScaleMfma& mf) {
-    if (hipMalloc(dev, h.blob.size()) != hipSuccess) throw std::runtime_error("upload_scale_frags: hipMalloc");
-    if (hipMemcpy(*dev, h.blob.data(), h.blob.size(), hipMemcpyHostToDevice) != hipSuccess)
+void upload_scale_frags(const ScaleFragsHost& h, GpuArena& res, ScaleMfma& mf) {
+    char* b = res.device<char>(h.blob.size());
+    if (hipMemcpy(b, h.blob.data(), h.blob.size(), hipMemcpyHostToDevice) != hipSuccess)
         throw std::runtime_error("upload_scale_frags: hipMemcpy");
-    const char* b = static_cast<const char*>(*dev);
     mf.gx = reinterpret_cast<const int*>(b + h.off_gx);
     mf.gy = reinterpret_cast<const int*>(b + h.off_gy);
     mf.fh = b + h.off_fh;

@@ -25,11 +25,7 @@ FramePool::FramePool(int width, int height, int slots) : w_(width), h_(height) {
     pitch_ = ((width * 4) + 255) & ~255;
     buf_.resize(slots, nullptr);
     gen_.assign(slots, 0);
-    for (auto& b : buf_) HIP_CHECK(hipMalloc(&b, (size_t)pitch_ * height));
-}
-
-FramePool::~FramePool() {
-    for (auto b : buf_) hipFree(b);
+    for (auto& b : buf_) b = res_.device<uint8_t>((size_t)pitch_ * height);
 }
 
 int FramePool::acquire() {
@@ -87,8 +83,8 @@ Session::Session(const SessionConfig& cfg) : cfg_(cfg) {
     cfg_.enc.mask_y0 = cfg_.mask_y0;
     cfg_.enc.mask_x1 = cfg_.mask_x1;
     cfg_.enc.mask_y1 = cfg_.mask_y1;
-    HIP_CHECK(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
-    pool_ = std::make_unique<FramePool>(cfg_.width, cfg_.height, cfg_.pool_slots);
+    stream_ = res_.stream(hipStreamNonBlocking);
+    pool_ =std::make_unique<FramePool>(cfg_.width, cfg_.height, cfg_.pool_slots);
     if ((cfg_.codec == "h264" || cfg_.codec == "avc") && cfg_.use_graph && cfg_.enc.deblock != 0 &&
         cfg_.enc.deblock != 1) {
         // the adaptive filter changes the picture's kernel sequence, a replayed graph cannot:
@@ -109,8 +105,8 @@ Session::Session(const SessionConfig& cfg) : cfg_(cfg) {
     depth_ = enc_->depth();
     if (depth_ > kMaxDepth) throw std::invalid_argument("Session: encoder pipeline depth above kMaxDepth");
     for (int k = 0; k < depth_; ++k) {
-        HIP_CHECK(hipMalloc(&nv12_y_[k], (size_t)g.pitch * g.coded_h));
-        HIP_CHECK(hipMalloc(&nv12_uv_[k], (size_t)g.pitch * g.coded_h / 2));
+        nv12_y_[k] = res_.device<uint8_t>((size_t)g.pitch * g.coded_h);
+        nv12_uv_[k] = res_.device<uint8_t>((size_t)g.pitch * g.coded_h / 2);
     }
     const std::string codec = enc_->codec();
     const bool cap = cfg_.capture_stream > 0 || (cfg_.capture_stream < 0 && (codec == "h264" || codec == "hevc"));
@@ -124,20 +120,19 @@ Session::Session(const SessionConfig& cfg) : cfg_(cfg) {
         if (cp && std::string(cp) == "low") {
             int least = 0, greatest = 0;
             HIP_CHECK(hipDeviceGetStreamPriorityRange(&least, &greatest));
-            HIP_CHECK(hipStreamCreateWithPriority(&cap_stream_, hipStreamNonBlocking, least));
+            cap_stream_ = res_.stream(hipStreamNonBlocking, least);
         } else {
-            HIP_CHECK(hipStreamCreateWithFlags(&cap_stream_, hipStreamNonBlocking));
+            cap_stream_ = res_.stream(hipStreamNonBlocking);
         }
         // GPU-to-GPU only: device-scope release where the event is recorded (scaler path); as the stop
         // event of k_bgrx_to_nv12 the runtime's launch path picks the release scope (not measured apart)
-        for (int k = 0; k < depth_; ++k)
-            HIP_CHECK(hipEventCreateWithFlags(&ev_conv_[k], hipEventDisableTiming | hipEventReleaseToDevice));
+        for (int k = 0; k < depth_; ++k) ev_conv_[k] = res_.event(hipEventDisableTiming | hipEventReleaseToDevice);
     }
     if (depth_ > 1 && cfg_.use_graph && !enc_->supports_split())
         throw std::invalid_argument("hipGraph replay with pipeline_depth 2 needs an encoder with the split form");
     if (depth_ >= cfg_.pool_slots) throw std::invalid_argument("pool_slots must exceed pipeline_depth");
     for (int k = 0; k < depth_; ++k)
-        HIP_CHECK(hipHostMalloc(&staging_[k], (size_t)pool_->pitch() * cfg_.height, hipHostMallocDefault));
+        staging_[k] = res_.pinned<uint8_t>((size_t)pool_->pitch() * cfg_.height, hipHostMallocDefault);
     scale_ = cfg_.out_width != cfg_.width || cfg_.out_height != cfg_.height;
     if (scale_) {
         std::vector<int> sx, sy;
@@ -146,8 +141,7 @@ Session::Session(const SessionConfig& cfg) : cfg_(cfg) {
         make_lanczos_table(cfg_.width, cfg_.out_width, sx, wx, tx);
         make_lanczos_table(cfg_.height, cfg_.out_height, sy, wy, ty);
         const size_t bytes = (sx.size() + sy.size()) * 4 + (wx.size() + wy.size()) * 4;
-        HIP_CHECK(hipMalloc(&lt_mem_, bytes));
-        char* p = static_cast<char*>(lt_mem_);
+        char* p = res_.device<char>(bytes);
         lt_.out_w = cfg_.out_width;
         lt_.out_h = cfg_.out_height;
         lt_.taps_x = tx;
@@ -168,37 +162,37 @@ Session::Session(const SessionConfig& cfg) : cfg_(cfg) {
         pix::ScaleFragsHost fr;
         if (!cfg_.scale_valu && pix::build_scale_frags(cfg_.width, cfg_.height, cfg_.out_width, cfg_.out_height,
                                                        eg.coded_w, eg.coded_h, sx, wx, tx, sy, wy, ty, fr))
-            pix::upload_scale_frags(fr, &lt_mf_mem_, lt_.mf);
+            pix::upload_scale_frags(fr, res_, lt_.mf);
     }
-    for (int k = 0; k < kMaxDepth; ++k) HIP_CHECK(hipEventCreate(&ev_start_[k]));
+    for (int k = 0; k < kMaxDepth; ++k) ev_start_[k] = res_.event(0);
     devclk_ = enc_->device_clock();
     clock_khz_ = device_clock_khz();
-    HIP_CHECK(hipHostMalloc(&ts_, sizeof(uint64_t) * cfg_.pool_slots, hipHostMallocMapped));
+    ts_ = res_.pinned<uint64_t>(cfg_.pool_slots, hipHostMallocMapped);
     std::memset(ts_, 0, sizeof(uint64_t) * cfg_.pool_slots);
     mask_in_encoder_ = enc_->masked_sse_in_encoder();
     if (masked() && !mask_in_encoder_) {
         const h264::Geometry& eg = enc_->geometry();
         const int nb = pix::sse_masked_blocks(eg.width, eg.height);
-        HIP_CHECK(hipMalloc(&mask_dev_, kMaxDepth * (size_t)nb * sizeof(unsigned long long)));
-        HIP_CHECK(hipMalloc(&mask_counter_, kMaxDepth * sizeof(unsigned int)));
+        mask_dev_ = res_.device<unsigned long long>(kMaxDepth * (size_t)nb);
+        mask_counter_ = res_.device<unsigned int>(kMaxDepth);
         HIP_CHECK(hipMemset(mask_counter_, 0, kMaxDepth * sizeof(unsigned int)));
         mask_stride_ = nb;
-        HIP_CHECK(hipHostMalloc(&mask_host_, kMaxDepth * sizeof(unsigned long long), hipHostMallocMapped));
-        for (int k = 0; k < kMaxDepth; ++k) HIP_CHECK(hipEventCreateWithFlags(&ev_mask_[k], hipEventDisableTiming));
+        mask_host_ = res_.pinned<unsigned long long>(kMaxDepth, hipHostMallocMapped);
+        for (int k = 0; k < kMaxDepth; ++k) ev_mask_[k] = res_.event(hipEventDisableTiming);
     }
     // one parameter block per frame slot: with two frames in flight a captured memcpy node may
     // run after the host has already written the next frame's parameters
-    HIP_CHECK(hipHostMalloc(&synth_host_, sizeof(pix::SynthParams) * cfg_.pool_slots, hipHostMallocDefault));
+    synth_host_ = res_.pinned<pix::SynthParams>(cfg_.pool_slots, hipHostMallocDefault);
     // static layer of the synthetic desktop, rendered once (k_synth copies it outside the
     // animated elements)
-    HIP_CHECK(hipMalloc(&synth_bg_, (size_t)pool_->pitch() * cfg_.height));
+    synth_bg_ = res_.device<uint8_t>((size_t)pool_->pitch() * cfg_.height);
     pix::launch_synth_static(synth_bg_, synth_params(), stream_);
     HIP_CHECK(hipGetLastError());
     // k_synth reads the static layer from cap_stream_ (a non-blocking stream with no order
     // against stream_) or from the upload stream: the layer must be complete before the first
     // frame is rendered on any of them
     HIP_CHECK(hipStreamSynchronize(stream_));
-    HIP_CHECK(hipMalloc(&synth_dev_, sizeof(pix::SynthParams) * cfg_.pool_slots));
+    synth_dev_ = res_.device<pix::SynthParams>(cfg_.pool_slots);
     // [frame slot][encoder slot][IDR][analysis, entropy]
     graphs_.assign((size_t)cfg_.pool_slots * kMaxDepth * 2 * 2, nullptr);
     t0_us_ = now_us();
@@ -217,35 +211,6 @@ Session::~Session() {
     enc_.reset();
     for (auto g : graphs_)
         if (g) hipGraphExecDestroy(g);
-    hipHostFree(synth_host_);
-    if (ts_) hipHostFree(ts_);
-    if (synth_bg_) hipFree(synth_bg_);
-    hipFree(synth_dev_);
-    pool_.reset();
-    if (cap_stream_) (void)hipStreamDestroy(cap_stream_);
-    for (int k = 0; k < kMaxDepth; ++k) {
-        if (nv12_y_[k]) (void)hipFree(nv12_y_[k]);
-        if (nv12_uv_[k]) (void)hipFree(nv12_uv_[k]);
-        if (ev_conv_[k]) (void)hipEventDestroy(ev_conv_[k]);
-    }
-    for (int k = 0; k < kMaxDepth; ++k)
-        if (staging_[k]) (void)hipHostFree(staging_[k]);
-    if (lt_mem_) hipFree(lt_mem_);
-    if (lt_mf_mem_) hipFree(lt_mf_mem_);
-    for (void* p : host_locked_) (void)hipHostUnregister(p);
-    if (screen_) (void)hipFree(screen_);
-    if (ev_upload_) (void)hipEventDestroy(ev_upload_);
-    if (upload_stream_) {
-        (void)hipStreamSynchronize(upload_stream_);
-        (void)hipStreamDestroy(upload_stream_);
-    }
-    for (int k = 0; k < kMaxDepth; ++k) (void)hipEventDestroy(ev_start_[k]);
-    if (mask_dev_) (void)hipFree(mask_dev_);
-    if (mask_counter_) (void)hipFree(mask_counter_);
-    if (mask_host_) (void)hipHostFree(mask_host_);
-    for (int k = 0; k < kMaxDepth; ++k)
-        if (ev_mask_[k]) (void)hipEventDestroy(ev_mask_[k]);
-    hipStreamDestroy(stream_);
 }
 
 bool Session::convert(int slot, hipStream_t st, uint64_t* ts, hipEvent_t done) {
@@ -454,15 +419,15 @@ void Session::register_host_buffer(const void* p, size_t bytes) {
             throw std::runtime_error(std::string("HIP error ") + hipGetErrorString(e) +
                                      " in register_host_buffer: hipHostRegister");
         }
-        host_locked_.push_back(const_cast<void*>(p));
+        res_.registered(const_cast<void*>(p));
     }
     host_regs_.emplace_back(b, bytes);
     ensure_upload_stream();
 }
 
 void Session::ensure_upload_stream() {
-    if (!ev_upload_) HIP_CHECK(hipEventCreateWithFlags(&ev_upload_, hipEventDisableTiming));
-    if (!upload_stream_) HIP_CHECK(hipStreamCreateWithFlags(&upload_stream_, hipStreamNonBlocking));
+    if (!ev_upload_) ev_upload_ = res_.event(hipEventDisableTiming);
+    if (!upload_stream_) upload_stream_ = res_.stream(hipStreamNonBlocking);
 }
 
 void Session::encode_uploaded(int slot, int k, bool force_idr) {
@@ -495,7 +460,7 @@ void Session::submit_bgrx_damage(const uint8_t* host_bgrx, int host_pitch, size_
     ensure_upload_stream();
     const size_t pitch = pool_->pitch();
     if (!screen_) {
-        HIP_CHECK(hipMalloc(&screen_, pitch * cfg_.height));
+        screen_ = res_.device<uint8_t>(pitch * cfg_.height);
         screen_valid_ = false;
     }
     std::vector<std::pair<int, int>> todo;

@@ -26,7 +26,6 @@ namespace mx {
 class FramePool {
    public:
     FramePool(int width, int height, int slots);
-    ~FramePool();
     FramePool(const FramePool&) = delete;
     FramePool& operator=(const FramePool&) = delete;
     int width() const { return w_; }
@@ -42,6 +41,7 @@ class FramePool {
 
    private:
     int w_, h_, pitch_;
+    GpuArena res_;  // owns the slots' memory: before buf_, so it is destroyed after it
     std::vector<uint8_t*> buf_;
     std::vector<uint64_t> gen_;
     int next_ = 0;
@@ -185,6 +185,10 @@ class Session {
     void capture_frame_graphs(int slot, bool idr, hipGraphExec_t* ga, hipGraphExec_t* ge);
 
     SessionConfig cfg_;
+    // Owns every stream, event, buffer and page-locked range of the session (the executable graphs
+    // stay in graphs_).  Declared before pool_ and enc_: the encoder runs on stream_, so the arena
+    // is destroyed after both.
+    GpuArena res_;
     hipStream_t stream_ = nullptr;
     std::unique_ptr<FramePool> pool_;
     std::unique_ptr<VideoEncoder> enc_;
@@ -200,10 +204,7 @@ class Session {
     // Lanczos tables (device) when out size != desktop size
     bool scale_ = false;
     pix::LanczosTables lt_{};
-    void* lt_mem_ = nullptr;
-    void* lt_mf_mem_ = nullptr;  // MFMA scaler fragment tables
     std::vector<std::pair<const uint8_t*, size_t>> host_regs_;  // register_host_buffer ranges
-    std::vector<void*> host_locked_;  // those of them this session page-locked (to unregister)
     hipEvent_t ev_upload_ = nullptr;
     hipStream_t upload_stream_ = nullptr;  // zero-copy DMA from registered capture buffers
     uint8_t* screen_ = nullptr;  // device-resident screen (submit_bgrx_damage), pool pitch

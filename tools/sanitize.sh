@@ -20,4 +20,7 @@ for s in "${SRC[@]}"; do
 done
 wait
 /opt/rocm/bin/hipcc --offload-arch=gfx950 $SAN "${objs[@]}" -o "$OUT/sanitize" -lssl -lcrypto
+# no device is visible to the program: its GPU encoder constructors fail at their first allocation
+# (sanitize_main.cpp unwinding_pass), on a host with a GPU as on one without
+HIP_VISIBLE_DEVICES=-1 ROCR_VISIBLE_DEVICES=-1 \
 ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 UBSAN_OPTIONS=print_stacktrace=1:halt_on_error=1 "$OUT/sanitize"

@@ -1,7 +1,7 @@
 // Host-side ASan/UBSan driver for the native code that parses or produces untrusted /
 // variable-length data: CPU H.264 / HEVC / VP8 encoders (same MB cores as the
 // HIP kernels), SRTP/SRTCP, DTLS-SRTP handshake, RTP H.264 / H.265 / VP8 packetizers, Annex-B
-// splitter.
+// splitter; the unwinding of a GPU encoder whose constructor fails.
 // Built by tools/sanitize.sh with -fsanitize on the host side only; no GPU is touched.
 #include <arpa/inet.h>
 #include <cstdio>
@@ -259,8 +259,38 @@ static void token_and_sender_pass(std::mt19937& rng) {
     close(tx);
 }
 
+// The GPU encoders' constructors where no device answers: the first acquisition fails, the
+// constructor throws, and what it built so far unwinds -- nothing stays with an arena, nothing leaks.
+template <class Enc>
+static void failed_constructor() {
+    h264::EncoderConfig c;
+    c.width = 208;
+    c.height = 112;
+    c.bitrate_kbps = 0;
+    bool threw = false;
+    try {
+        Enc enc(c, nullptr);
+    } catch (const std::runtime_error&) {
+        threw = true;
+    }
+    CHECK(threw);
+    CHECK(GpuArena::live() == 0);
+}
+
+static void unwinding_pass() {
+    int n = 0;
+    if (hipGetDeviceCount(&n) == hipSuccess && n > 0) {  // tools/sanitize.sh hides the devices
+        std::printf("unwinding pass skipped: a HIP device is visible\n");
+        return;
+    }
+    failed_constructor<h264::GpuH264Encoder>();
+    failed_constructor<hevc::GpuHevcEncoder>();
+    failed_constructor<vp8::GpuVp8Encoder>();
+}
+
 int main() {
     std::mt19937 rng(12345);
+    unwinding_pass();
     token_and_sender_pass(rng);
     encoder_pass(rng);
     hevc_pass(rng);

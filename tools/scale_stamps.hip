@@ -67,8 +67,8 @@ int main(int argc, char** argv) {
         return 2;
     }
     LanczosTables t{out_w, out_h, tx, ty, nullptr, nullptr, nullptr, nullptr};
-    void* frags = nullptr;
-    upload_scale_frags(fr, &frags, t.mf);
+    mx::GpuArena frags;
+    upload_scale_frags(fr, frags, t.mf);
     std::vector<uint8_t> host((size_t)in_w * in_h * 4);
     std::mt19937 rng(7);
     for (size_t i = 0; i < host.size(); i += 4) {  // smooth-ish content with noise
@@ -96,7 +96,6 @@ int main(int argc, char** argv) {
 #ifndef MX_SCALE_STAMPS  // the production kernel: launch timing only (run it under rocprofv3)
     printf("%dx%d -> %dx%d: %d workgroups, lds_cols %d, %.2f us per launch (events, %d back-to-back)\n", in_w, in_h,
            out_w, out_h, nwg, fr.lds_cols, 1e3 * ms / reps, reps);
-    HIP_CHECK(hipFree(frags));
     return 0;
 #else
     if (nwg > 4096) return 3;
@@ -129,7 +128,6 @@ int main(int argc, char** argv) {
     }
     printf("us : started / resident\n");
     for (int b = 0; b < nb; ++b) printf("%3d : %4d / %4d\n", b, hist[b], live[b]);
-    HIP_CHECK(hipFree(frags));
     return 0;
 #endif
 }
